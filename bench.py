@@ -1,6 +1,20 @@
 """bench.py — simulated peer-rounds/s of the MI355X SWIM-round simulator (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--nodes 65536] [--loss 0.01] [--churn 0.001]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it builds the mesh, steps W warmup rounds, times K steps, writes
+the outputs when --dump-outputs is given, and prints one JSON line (metric, value, unit, ms_per_step, ..., and
+what the timed rounds themselves measured: round_gpu_ms, host_syncs_per_round, round_roofline, and `kernels` /
+`roofline` over the kernels that carry events in the timed rounds).  Every further measurement that needs a run
+of its own (the profiled replay, convergence, cpu_baseline, modes, seeds; "Also reported" below) is behind --full.
+
+--dump-outputs DIR (N = 1): after the timed steps, what a caller of the timed path holds after its last step, as
+DIR/<name>.npy (float64, the stamp rows float32; exact for these integers), under 64 MB in all: `stats`
+(kb_sim_stats, the counters in KbStats field order), `fingerprints` and `scalars` (kb_sim_fingerprints,
+kb_sim_dump_scalars) of the peers listed in `peers_index`, and `rows_sample` (kb_sim_dump_row) of the rows listed
+in `rows_index`.  The two index lists are fixed seeded samples (every peer up to DUMP_PEERS ids), and the
+simulation is deterministic, so the same arguments give the same files from run to run and from build to build.
 
 Workload (BASELINE.json configs[2]): 65,536 simulated Kaboodle peers on one MI355X, started converged,
 1% per-delivery loss and 0.1%/round churn (leaves + joins with fresh ids).  A "step" is one complete
@@ -16,7 +30,7 @@ configs[3]: --weak --nodes 131072 on 8 GPUs = 1M peers); its rows get wider with
 tracks every peer, so per-GPU work grows with N.  --replicas runs N independent meshes instead
 (distinct seeds, no collective on the data path).
 
-Also reported, on the same JSON line:
+Also reported with --full, on the same JSON line:
   kernels       every kernel of the round: HIP-event ms per round (each launch timed by its own dispatch
                 packet on the simulator's stream), launches per round, wave-0 share, and for the kernels
                 with an in-kernel byte counter (k_rowpass, k_fold, k_resp_wave, k_proc) the algorithmic
@@ -57,6 +71,8 @@ KT_ROUND = 1                    # kb_sim_kernel_time kind of the whole round
 # kernels on the simulator's side stream (kb_sim.hip step_round: side_fork / side_join), overlapping the round's
 SIDE_KERNELS = ("k_alive_bits", "k_truefp_part", "k_truefp_fin", "k_lat_sweep", "k_a3_exact")
 CHURN_RESERVE = 8192            # fresh ids kept for churn joins: capacity does not depend on --steps
+DUMP_PEERS = 1 << 18            # --dump-outputs: fingerprints and scalars of at most this many ids (12.6 MB as float64)
+DUMP_ROW_BYTES = 40 << 20       # --dump-outputs: float32 bytes of the sampled stamp rows
 
 
 def parse(argv=None):
@@ -72,6 +88,11 @@ def parse(argv=None):
     ap.add_argument("--loss", type=float, default=0.01)
     ap.add_argument("--churn", type=float, default=0.001)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: write the mesh state after the last timed step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the profiled replay, convergence, the CPU baseline, the other modes and seeds "
+                         "(each can be dropped again with its --no-* option)")
     ap.add_argument("--conv-cap", type=int, default=100, help="max untimed quiescent rounds for convergence")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline sample budget")
     ap.add_argument("--cpu1-seconds", type=float, default=15.0, help="single-thread CPU sample budget (0: skip)")
@@ -168,6 +189,33 @@ def timed_rounds(mesh, steps: int, world: int):
     s1 = mesh.stats()                                # sharded: the whole mesh (collective)
     # live peers of every simulated round, counted on the device during the round (kb_stats.alive_rounds)
     return dt, s1["alive_rounds"] - s0["alive_rounds"], s0, s1
+
+
+def seeded_sample(n: int, k: int):
+    """Every id below n, or a fixed sample of k of them (sorted; the same ids in every run)."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(0).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(mesh, stats: dict, out_dir: str) -> None:
+    """--dump-outputs: the state a caller of kb_sim_step reads back after the last timed step (module docstring)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = mesh.capacity
+    peers = seeded_sample(cap, DUMP_PEERS)
+    rows = seeded_sample(cap, max(1, DUMP_ROW_BYTES // (4 * cap)))
+    arrays = {
+        "stats": np.array([stats[k] for k in stats], dtype=np.float64),
+        "peers_index": peers.astype(np.float64),
+        "fingerprints": mesh.fingerprints()[peers].astype(np.float64),
+        "scalars": mesh.scalars()[peers].astype(np.float64),
+        "rows_index": rows.astype(np.float64),
+        "rows_sample": np.stack([mesh.row(int(i)) for i in rows]).astype(np.float32),
+    }
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def round_model_bytes(s0: dict, s1: dict, alive_mean: float, steps: int) -> float:
@@ -272,11 +320,13 @@ def aggregate(dt: float, units: float, world: int, device="cpu"):
     return float(tm[0]), float(tu[0])
 
 
-def main() -> int:
-    a = parse()
+def main(argv=None) -> int:
+    a = parse(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+    if a.dump_outputs and (world > 1 or a.rank_mesh):
+        raise SystemExit("--dump-outputs reads the whole mesh from one process: N = 1, without --rank-mesh")
     import torch
     import torch.distributed as dist
     if world > 1:
@@ -310,12 +360,14 @@ def main() -> int:
     bd = mesh.kernel_breakdown()
     round_ms, round_n = mesh.kernel_time(KT_ROUND)
     model_bytes = round_model_bytes(st0, st, alive_sum / max(a.steps, 1), a.steps)
+    if a.dump_outputs:
+        dump_outputs(mesh, st, a.dump_outputs)       # before anything below steps the mesh further
 
     # sharded: every rank saw the whole mesh's count, so it enters the sum once
     dt, alive_total = aggregate(dt, float(alive_sum if (rank == 0 or not shard) else 0), world, device="cuda")
 
     conv = None
-    if not a.no_conv:
+    if a.full and not a.no_conv:
         # (1) BASELINE configs[1]: 1024 peers all joining at round 0, no faults -> rounds to convergence
         r2 = -1
         if rank == 0 or not shard:
@@ -354,7 +406,7 @@ def main() -> int:
             conv["workload_view_size_mean_gap_final"] = round(float(gap.mean()), 2)
 
     # every kernel's time: an untimed replay of the same rounds (deterministic) with events on every launch
-    if world == 1 and not a.no_replay:
+    if a.full and world == 1 and not a.no_replay:
         mesh.close()
         with kaboodle_amd.Mesh(cfg) as rp:
             rp.set_profiling(2)
@@ -401,7 +453,7 @@ def main() -> int:
         out = {
             "metric": "simulated peer-rounds/sec (whole node) + rounds to fingerprint convergence",
             "value": alive_total / dt, "unit": "peer-rounds/s", "n_gpus": world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True,
+            "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "full": a.full,
             "scaling": "weak" if (getattr(a, "weak", False) or (world > 1 and not shard)) else "strong",
             "vs_baseline": None, "dtype": "u8",
             "data": "synthetic (Philox-keyed loss/churn/targets, seed-determined)",
@@ -421,14 +473,14 @@ def main() -> int:
                                "unit": "GB/s", "frac": round(model_bytes / (dt / a.steps) / 1e9 / HBM_PEAK_GBS, 4)},
             "convergence": conv,
         }
-        if world == 1 and not a.no_cpu:
+        if a.full and world == 1 and not a.no_cpu:
             ccfg = SimConfig(**{**cfg.__dict__, "device": -1})
             out["cpu_baseline"] = cpu_baseline(ccfg, a.cpu_seconds, a.nodes, a.cpu1_seconds)
         else:
             out["cpu_baseline"] = None
     mesh.close()
     modes = None
-    if world == 1 and not a.no_modes and a.failed_mode == "sim_sender":
+    if a.full and world == 1 and not a.no_modes and a.failed_mode == "sim_sender":
         # Q1's deployment-faithful reading (Failed never honoured, src/networking.rs:44-55): same
         # workload, seeds, K and W, its own mesh; timed the same way
         import copy
@@ -475,7 +527,7 @@ def main() -> int:
                                            for n, k in sorted(kb4.items(), key=lambda kv: -kv[1]["ms"])[:12]}
         modes["exact_lru" if other == "exact" else "window"] = ent
     seeds = None
-    if world == 1 and a.seeds:
+    if a.full and world == 1 and a.seeds:
         # seeds 2 and 3 of the same synthetic workload, same K and W, each its own mesh
         import copy
         seeds = {}

@@ -26,6 +26,51 @@ def test_capacity_independent_of_steps():
     assert caps == {65536 + bench.CHURN_RESERVE}
 
 
+def test_plain_run_is_the_default():
+    """--full is off unless asked for, and changes nothing about the timed workload."""
+    plain = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    full = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert plain.full is False and plain.dump_outputs is None and full.full is True
+    assert bench.rank_config(plain, 0, 1, 0) == bench.rank_config(full, 0, 1, 0)
+
+
+def test_seeded_sample_is_fixed():
+    import numpy as np
+    assert np.array_equal(bench.seeded_sample(5, 8), np.arange(5))
+    s = bench.seeded_sample(73728, 142)
+    assert len(s) == 142 and len(np.unique(s)) == 142 and s.min() >= 0 and s.max() < 73728
+    assert np.array_equal(s, np.sort(s)) and np.array_equal(s, bench.seeded_sample(73728, 142))
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs writes float arrays of the state after the last step; here through the oracle, which
+    implements the same ABI (the GPU run of the same code: tests/test_gpu_bench.py)."""
+    import numpy as np
+    import parity
+    from kaboodle_amd._ffi import KB_INIT_CONVERGED, Sim, SimConfig
+    cfg = SimConfig(capacity=96, initial_nodes=64, init_mode=KB_INIT_CONVERGED, loss=0.02, churn=0.01, seed=3)
+    with Sim(parity.oracle_lib(), cfg) as o:
+        o.step(4)
+        st = o.stats()
+        bench.dump_outputs(o, st, str(tmp_path / "out"))
+        got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in
+               ("stats", "peers_index", "fingerprints", "scalars", "rows_index", "rows_sample")}
+        assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+        assert np.array_equal(got["stats"], [st[k] for k in st]) and got["stats"][0] == 4       # round
+        assert np.array_equal(got["peers_index"], np.arange(96)) and np.array_equal(got["rows_index"], np.arange(96))
+        assert np.array_equal(got["fingerprints"], o.fingerprints())
+        assert np.array_equal(got["scalars"], o.scalars())
+        assert np.array_equal(got["rows_sample"], o.rows())
+
+
+def test_dump_outputs_size_bound():
+    """Under 64 MB in all at the benched size and at configs[3]'s 1M ids."""
+    for cap in (65536 + bench.CHURN_RESERVE, 1 << 20):
+        peers = len(bench.seeded_sample(cap, bench.DUMP_PEERS))
+        rows = len(bench.seeded_sample(cap, max(1, bench.DUMP_ROW_BYTES // (4 * cap))))
+        assert 8 * 40 + peers * 8 * 6 + rows * 8 + rows * cap * 4 < 64 << 20
+
+
 def test_records_match_by_binary_or_sources(tmp_path, monkeypatch):
     """bench.py attaches a PMC or convergence record made with this library: the same binary, or (hipcc's output
     is not byte-reproducible) the same build inputs; a change to any input changes the source identity."""
