@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "kaboodle_sim.h"
+#include "kaboodle_census.h"
 
 namespace kb {
 
@@ -34,17 +35,29 @@ inline std::string format_addr(uint32_t id) {                 // canonical simul
 
 class Mesh {
  public:
-  explicit Mesh(const kb_config& cfg) { check(kb_sim_create(&cfg, &h_), "kb_sim_create"); }
+  explicit Mesh(const kb_config& cfg) : capacity_(cfg.capacity) { check(kb_sim_create(&cfg, &h_), "kb_sim_create"); }
   static kb_config defaults() { kb_config c; kb_config_default(&c); return c; }
   ~Mesh() { if (h_) kb_sim_destroy(h_); }
   Mesh(const Mesh&) = delete;
   Mesh& operator=(const Mesh&) = delete;
-  Mesh(Mesh&& o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
+  Mesh(Mesh&& o) noexcept : h_(std::exchange(o.h_, nullptr)), capacity_(o.capacity_) {}
 
   void step(uint32_t rounds = 1) { check(kb_sim_step(h_, rounds), "kb_sim_step"); }
   kb_stats stats() const { kb_stats s; check(kb_sim_stats(h_, &s), "kb_sim_stats"); return s; }
   uint32_t true_fingerprint() const { uint32_t f; check(kb_sim_true_fingerprint(h_, &f), "kb_sim_true_fingerprint"); return f; }
   kb_sim* handle() const { return h_; }
+
+  // the view census (kaboodle_census.h; HIP library only): who knows whom, mesh-wide, counted on the device.
+  // arrays = false asks for the summary alone.
+  struct Census { kb_census summary; std::vector<uint32_t> known_by, missing, stale; };
+  Census census(bool arrays = true) const {
+    Census c;
+    if (arrays) { c.known_by.resize(capacity_); c.missing.resize(capacity_); c.stale.resize(capacity_); }
+    check(kb_sim_census(h_, &c.summary, arrays ? c.known_by.data() : nullptr, c.known_by.size(),
+                        arrays ? c.missing.data() : nullptr, arrays ? c.stale.data() : nullptr, c.missing.size()),
+          "kb_sim_census");
+    return c;
+  }
 
   // the per-instance view: method names of src/lib.rs
   class Peer {
@@ -135,6 +148,7 @@ class Mesh {
 
  private:
   kb_sim* h_ = nullptr;
+  uint32_t capacity_ = 0;
 };
 
 }  // namespace kb

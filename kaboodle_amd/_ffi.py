@@ -73,6 +73,21 @@ class KbKernelTime(C.Structure):
                 ("has_bytes", C.c_uint32), ("pad", C.c_uint32), ("wave_ms", C.c_double * KB_WAVE_SLOTS)]
 
 
+class KbCensus(C.Structure):
+    """kb_census (include/kaboodle_census.h)."""
+    _fields_ = [("round", C.c_int32), ("observers", C.c_uint32), ("running", C.c_uint32), ("exact_views", C.c_uint32),
+                ("pairs", C.c_uint64), ("missing", C.c_uint64), ("stale", C.c_uint64),
+                ("full_ids", C.c_uint32), ("ghost_ids", C.c_uint32), ("least_known", C.c_uint32),
+                ("least_known_by", C.c_uint32), ("top_ghost", C.c_uint32), ("top_ghost_by", C.c_uint32),
+                ("reserved", C.c_uint64 * 4)]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+KB_CENSUS_NONE = 0xFFFFFFFF
+
+
 class KbWireAddrC(C.Structure):
     _fields_ = [("ip", C.c_uint8 * 4), ("port", C.c_uint16), ("pad", C.c_uint16)]
 
@@ -205,6 +220,10 @@ _OPTIONAL = {
     "sim_kernel_breakdown": (C.c_int, [C.c_void_p, C.POINTER(KbKernelTime), C.c_size_t, C.POINTER(C.c_size_t)]),
     "sim_host_syncs": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "sim_sparse_footprint": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t]),
+    # the view census (include/kaboodle_census.h; HIP library only, the oracle answers through census.census_ref)
+    "sim_census": (C.c_int, [C.c_void_p, C.POINTER(KbCensus), C.POINTER(C.c_uint32), C.c_size_t,
+                             C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t]),
+    "sim_census_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
 }
 
 
@@ -274,6 +293,7 @@ class Sim:
             lib.call("sim_create", C.byref(self._c), C.byref(h))
         self.h = h
         self.capacity = cfg.capacity
+        self.external: set[int] = set()      # ids marked by set_external (census_ref needs them on the oracle)
 
     def shard_info(self):
         """(rank, world, lo, hi): the rows this handle holds."""
@@ -421,6 +441,7 @@ class Sim:
     def set_external(self, node: int) -> None:
         """Mark a never-bound address as an external peer (kb_sim_set_external)."""
         self.lib.call("sim_set_external", self.h, node)
+        self.external.add(node)
 
     def inject(self, sender: int, dest: int, kind: int, a: int = 0, fp: int = 0, n: int = 0, ids=()) -> None:
         """Queue a record from external peer `sender` to `dest` for the next round's wave 0 (kb_sim_inject);
@@ -444,6 +465,32 @@ class Sim:
         st = KbStats()
         self.lib.call("sim_stats", self.h, C.byref(st))
         return st.as_dict()
+
+    def census(self, arrays: bool = True):
+        """The view census (include/kaboodle_census.h): a `Census` with `summary` (dict of kb_census) and the
+        uint32 arrays `known_by`, `missing`, `stale` over all ids (None with arrays=False: the summary alone).
+        Computed on the device by kb_sim_census; a library without it (the CPU oracle) answers the same call
+        through census.census_ref, so both are compared through identical calls.  With arrays the Census also
+        carries `running` (for the Tracker), which costs one scalars() download per call (kb_sim_census does not
+        return the running set); arrays=False skips it."""
+        from .census import Census, census_ref
+        if "sim_census" not in self.lib.fn:
+            return census_ref(self)
+        import numpy as np
+        out = KbCensus()
+        if not arrays:
+            self.lib.call("sim_census", self.h, C.byref(out), None, 0, None, None, 0)
+            return Census(out.as_dict(), None, None, None)
+        kb, mi, st = (np.zeros(self.capacity, dtype=np.uint32) for _ in range(3))
+        ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        self.lib.call("sim_census", self.h, C.byref(out), ptr(kb), self.capacity, ptr(mi), ptr(st), self.capacity)
+        return Census(out.as_dict(), kb, mi, st, self.scalars()[:, 0] != 0)
+
+    def census_device_ms(self) -> float:
+        """Device time of the last census() in ms (kb_sim_census_device_ms; HIP library only)."""
+        v = C.c_double()
+        self.lib.call("sim_census_device_ms", self.h, C.byref(v))
+        return v.value
 
     def row(self, node: int):
         import numpy as np

@@ -1,0 +1,357 @@
+// kb_census.h — the view census (include/kaboodle_census.h): for every id the number of running
+// rows whose view holds it, and for every running row how far its view is from the running set.  Included at
+// the end of kb_sim.hip; reads the engines' state, writes only its own scratch.
+//
+// Dense engine: one streaming pass over the member bits (Dev::bits, [rows][W/32]).  A lane owns one 16-byte
+// column group (4 words = 128 ids) and walks down a tile of rows, so each row read is 1 KiB contiguous per
+// wave.  The column counts are BIT-SLICED: a word of a row is added into 5 bit-planes with a ripple of
+// half adders (plane p holds bit p of 32 vertical counters at once), the 5 planes are added into 12 more
+// every 24 rows, and only at the end of the tile is each of the lane's 128 counters read out of the planes.
+// A workgroup's 4 waves (4 row tiles of one column block) combine their counters in LDS and add them to the
+// [W] result with integer atomics: order-free, so the result is deterministic.  The per-row counts (|view|,
+// running members, stale members) come in the same pass: three popcounts per word against loop-invariant
+// masks, a DPP reduction per row.
+//
+// Sparse rows: known_by[j] = B·base[j] + Σ over running rows of their exception entries (−1 for a based row's
+// exception that is a base member, +1 otherwise), B = running rows that adopted the base: O(entries) signed
+// atomics into a delta array, then one finishing kernel over the ids.  The rows' counts follow the same way
+// from the base's counts.
+#pragma once
+#include "../../include/kaboodle_census.h"
+
+namespace kb {
+
+constexpr uint32_t CS_LOW = 5, CS_HIGH = 12;      // bit planes: 5 filled row by row, folded into 12 more
+constexpr uint32_t CS_U = 8;                      // rows per batch (16-byte loads in flight per lane)
+constexpr uint32_t CS_FOLD = 24;                  // rows between folds (<= 2^CS_LOW - 1, a multiple of CS_U)
+constexpr uint32_t CS_MAX_RPW = 4080;             // rows per wave (< 2^CS_HIGH, a multiple of CS_FOLD)
+constexpr uint32_t CS_COLS = 8192;                // ids per column block: 64 lanes x 128
+constexpr uint32_t CS_LDS = 128 * 65;             // the block's counters: [word of the group][bit][lane], padded
+
+struct CsDense {
+  uint32_t* kb;                                   // [W] known_by (zeroed)
+  uint32_t* rowc;                                 // [3][R] |view|, running members, stale members (zeroed)
+  uint32_t* ab; uint32_t* sb; uint32_t* vb;       // [W/32] running ids, stale-class ids (neither running nor
+                                                  // external), valid ids (< C)
+  uint32_t rpw;                                   // rows per wave
+};
+
+// the running set as k_alive_bits builds it, and beside it the ids that are neither running nor external
+__global__ void k_cs_masks(Dev d, CsDense a) {
+  const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= d.NWR) return;
+  uint32_t x = 0, s = 0, v = 0;
+  for (uint32_t t = 0; t < 32; ++t) {
+    const uint32_t j = w * 32 + t;
+    if (j >= d.C) break;
+    const bool al = d.alive[j] != 0, ex = d.ext[j] != 0;
+    v |= 1u << t;
+    if (al) x |= 1u << t;
+    if (!al && !ex) s |= 1u << t;
+  }
+  a.ab[w] = x; a.sb[w] = s; a.vb[w] = v;
+}
+
+// x joins the vertical counters of planes p[0..N): a ripple of half adders (the carry out of the top plane
+// is zero while fewer than 2^N words have been added)
+template <uint32_t N> __device__ __attribute__((always_inline)) inline void cs_add1(uint32_t (&p)[N], uint32_t x) {
+#pragma unroll
+  for (uint32_t k = 0; k < N; ++k) { const uint32_t c = p[k] & x; p[k] ^= x; x = c; }
+}
+// the low planes' counters are added to the high planes' (full adders, then the carry's ripple) and cleared
+__device__ __attribute__((always_inline)) inline void cs_fold(uint32_t (&h)[CS_HIGH], uint32_t (&l)[CS_LOW]) {
+  uint32_t c = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < CS_LOW; ++k) {
+    const uint32_t s = h[k] ^ l[k];
+    const uint32_t c2 = (h[k] & l[k]) | (s & c);
+    h[k] = s ^ c; c = c2; l[k] = 0;
+  }
+#pragma unroll
+  for (uint32_t k = CS_LOW; k < CS_HIGH; ++k) { const uint32_t c2 = h[k] & c; h[k] ^= c; c = c2; }
+}
+
+// grid (W / 8192 column blocks, row tiles of 4 x rpw rows), 256 threads
+__global__ __launch_bounds__(256) void k_cs_dense(Dev d, CsDense a) {
+  __shared__ uint32_t cnt[CS_LDS];
+  for (uint32_t k = threadIdx.x; k < CS_LDS; k += 256) cnt[k] = 0;
+  __syncthreads();
+  const uint32_t l = lane();
+  const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint32_t nw4 = d.NWR / 4;
+  const uint32_t cg = blockIdx.x * 64 + l;                       // this lane's column group (< nw4: the grid is exact)
+  const uint4 ab = reinterpret_cast<const uint4*>(a.ab)[cg];
+  const uint4 sb = reinterpret_cast<const uint4*>(a.sb)[cg];
+  const uint4 vb = reinterpret_cast<const uint4*>(a.vb)[cg];
+  const uint64_t first = (uint64_t)d.lo + (uint64_t)(blockIdx.y * 4 + wv) * a.rpw;
+  const uint32_t r0 = first < d.hi ? (uint32_t)first : d.hi;
+  const uint32_t r1 = d.hi - r0 > a.rpw ? r0 + a.rpw : d.hi;
+  const uint4* rows = reinterpret_cast<const uint4*>(d.bits);
+  uint32_t lo[4][CS_LOW] = {}, hi[4][CS_HIGH] = {};
+  uint32_t nlow = 0;
+  for (uint32_t r = r0; r < r1; r += CS_U) {
+    uint32_t am = 0;                                             // the batch's running rows: a scalar mask
+#pragma unroll
+    for (uint32_t u = 0; u < CS_U; ++u) if (r + u < r1 && d.alive[r + u]) am |= 1u << u;
+    am = (uint32_t)__builtin_amdgcn_readfirstlane((int)am);
+    if (!am) continue;                                           // no running row: nothing is read
+    uint4 v[CS_U];
+#pragma unroll
+    for (uint32_t u = 0; u < CS_U; ++u) {                        // every load of the batch before its first use
+      const uint32_t rr = r + u < r1 ? r + u : r1 - 1;
+      v[u] = rows[(size_t)rr * nw4 + cg];
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < CS_U; ++u) {
+      if (!((am >> u) & 1u)) continue;                           // a scalar branch: the row is not an observer
+      const uint32_t x0 = v[u].x & vb.x, x1 = v[u].y & vb.y, x2 = v[u].z & vb.z, x3 = v[u].w & vb.w;
+      cs_add1(lo[0], x0); cs_add1(lo[1], x1); cs_add1(lo[2], x2); cs_add1(lo[3], x3);
+      const uint32_t nv = __popc(x0) + __popc(x1) + __popc(x2) + __popc(x3);
+      const uint32_t nr = __popc(x0 & ab.x) + __popc(x1 & ab.y) + __popc(x2 & ab.z) + __popc(x3 & ab.w);
+      const uint32_t ns = __popc(x0 & sb.x) + __popc(x1 & sb.y) + __popc(x2 & sb.z) + __popc(x3 & sb.w);
+      const uint32_t t0 = wave_sum(nv | (nr << 16));             // <= 8192 each per wave: 16 bits hold them
+      const uint32_t t1 = wave_sum(ns);
+      if (l == 0) {
+        const size_t R = d.hi - d.lo, k = r + u - d.lo;
+        if (t0 & 0xFFFFu) atomicAdd(&a.rowc[k], t0 & 0xFFFFu);
+        if (t0 >> 16) atomicAdd(&a.rowc[R + k], t0 >> 16);
+        if (t1) atomicAdd(&a.rowc[2 * R + k], t1);
+      }
+    }
+    nlow += CS_U;
+    if (nlow == CS_FOLD) {
+#pragma unroll
+      for (uint32_t q = 0; q < 4; ++q) cs_fold(hi[q], lo[q]);
+      nlow = 0;
+    }
+  }
+#pragma unroll
+  for (uint32_t q = 0; q < 4; ++q) cs_fold(hi[q], lo[q]);
+  // the lane's 128 counters out of the planes, into the block's LDS counters (consecutive lanes, consecutive banks)
+  for (uint32_t c = 0; c < 32; ++c) {
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+      uint32_t n = 0;
+#pragma unroll
+      for (uint32_t p = 0; p < CS_HIGH; ++p) n |= ((hi[q][p] >> c) & 1u) << p;
+      if (n) atomicAdd(&cnt[(q * 32 + c) * 65 + l], n);
+    }
+  }
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < CS_COLS; k += 256) {        // id blockIdx.x * 8192 + k: lane k / 128, word, bit
+    const uint32_t n = cnt[(((k >> 5) & 3u) * 32 + (k & 31u)) * 65 + (k >> 7)];
+    if (n) atomicAdd(&a.kb[(size_t)blockIdx.x * CS_COLS + k], n);
+  }
+}
+
+// ---- sparse rows ---------------------------------------------------------------------------------------
+struct CsSparse {
+  int32_t* delta;                                 // [C] signed exception counts (zeroed)
+  uint32_t* kb;                                   // [C] known_by
+  uint32_t* rowc;                                 // [3][R] |view|, running members, stale members
+  uint32_t* acc;                                  // [4] base ∩ running, base ∩ stale class, B, spare (zeroed)
+};
+// the base's counts: its running members and its members that are neither running nor external
+__global__ __launch_bounds__(256) void k_cs_sp_base(SpDev d, CsSparse a) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t run = 0, st = 0;
+  if (j < d.C && sp_bbit(d, j)) {
+    const bool al = d.alive[j] != 0;
+    run = al; st = !al && !d.ext[j];
+  }
+  const uint32_t t = wave_sum(run | (st << 16));
+  if (lane() == 0 && t) {
+    if (t & 0xFFFFu) atomicAdd(&a.acc[0], t & 0xFFFFu);
+    if (t >> 16) atomicAdd(&a.acc[1], t >> 16);
+  }
+}
+// a thread per local row: its exceptions into the delta array and its own counts
+__global__ __launch_bounds__(256) void k_cs_sp_rows(SpDev d, CsSparse a) {
+  const uint32_t i = sp_gid(d);
+  const bool obs = i < d.hi && d.alive[i];
+  const bool based = obs && d.based[i];
+  const uint64_t nb = __ballot(based);
+  if (nb && lane() == (uint32_t)__builtin_ctzll(nb)) atomicAdd(&a.acc[2], (uint32_t)__popcll(nb));
+  if (!obs) return;
+  const uint32_t n = d.ne[i];
+  const uint4* e4 = reinterpret_cast<const uint4*>(sp_row(d, i));
+  int32_t dv = 0, dr = 0, ds = 0;
+  for (uint32_t g = 0; g < (n + 3u) >> 2; ++g) {                 // 16-byte loads (rows are 16-byte aligned)
+    const uint4 w4 = e4[g];
+    const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+      const bool on = g * 4 + q < n && (w[q] & SP_XF);
+      // the lanes of a wave that hold the same exception as its first such lane add it once between them: an id
+      // that left sits in every row's list, at the same place wherever the lists are otherwise alike
+      const uint32_t j = w[q] >> 9;
+      const int32_t sg = on && based && sp_bbit(d, j) ? -1 : 1;
+      const uint32_t key = on ? (j << 1) | (sg < 0 ? 1u : 0u) : 0xFFFFFFFFu;
+      const uint64_t act = __ballot(on);
+      if (!act) continue;
+      const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, __builtin_ctzll(act));
+      const uint64_t same = __ballot(on && key == k0);
+      if (on) {
+        if (key == k0) { if (lane() == (uint32_t)__builtin_ctzll(same)) atomicAdd(&a.delta[j], sg * (int32_t)__popcll(same)); }
+        else atomicAdd(&a.delta[j], sg);
+        const bool al = d.alive[j] != 0;
+        dv += sg; if (al) dr += sg; else if (!d.ext[j]) ds += sg;
+      }
+    }
+  }
+  const size_t R = d.hi - d.lo, k = i - d.lo;
+  a.rowc[k] = (uint32_t)((int32_t)(based ? d.nb : 0u) + dv);
+  a.rowc[R + k] = (uint32_t)((int32_t)(based ? a.acc[0] : 0u) + dr);
+  a.rowc[2 * R + k] = (uint32_t)((int32_t)(based ? a.acc[1] : 0u) + ds);
+}
+__global__ __launch_bounds__(256) void k_cs_sp_finish(SpDev d, CsSparse a) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < d.C) a.kb[j] = (uint32_t)((int32_t)(sp_bbit(d, j) ? a.acc[2] : 0u) + a.delta[j]);
+}
+
+}  // namespace kb
+
+// ---- host side -------------------------------------------------------------------------------------------
+// one handle's part of a census: known_by over all ids from its rows, the row counts at its rows' ids
+struct CsPart {
+  std::vector<uint32_t> kb, view, run, stale;     // [C] each (rows the handle does not hold: 0)
+  std::vector<uint8_t> alive, ext;                // [C] replicated facts
+  std::vector<uint8_t> held;                      // [C] 1 = a row of this handle (or of a shard already added)
+  double ms = 0;
+};
+static void cs_part_init(CsPart& p, uint32_t C) {
+  p.kb.assign(C, 0); p.view.assign(C, 0); p.run.assign(C, 0); p.stale.assign(C, 0); p.held.assign(C, 0);
+}
+struct CsTimer {
+  hipEvent_t a = nullptr, b = nullptr;
+  bool start(hipStream_t st) { return hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess && hipEventRecord(a, st) == hipSuccess; }
+  void stop(hipStream_t st) { (void)hipEventRecord(b, st); }
+  double ms() { float t = 0; if (a && b && hipEventElapsedTime(&t, a, b) != hipSuccess) t = 0; return t; }
+  ~CsTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
+// the rows' counts of a shard (device [3][R]) and its known_by land in the part, added to what is there
+static int cs_collect(CsPart& p, uint32_t C, uint32_t lo, uint32_t R, const uint32_t* d_kb, const uint32_t* d_rowc,
+                      const uint8_t* d_alive, const uint8_t* d_ext, hipStream_t st) {
+  std::vector<uint32_t> kb(C), rc(3ull * R);
+  p.alive.resize(C); p.ext.resize(C);
+  HIPCHK(hipMemcpyAsync(kb.data(), d_kb, 4ull * C, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(rc.data(), d_rowc, 12ull * R, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(p.alive.data(), d_alive, C, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(p.ext.data(), d_ext, C, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (uint32_t j = 0; j < C; ++j) p.kb[j] += kb[j];
+  for (uint32_t k = 0; k < R; ++k) {
+    p.view[lo + k] = rc[k]; p.run[lo + k] = rc[R + k]; p.stale[lo + k] = rc[2ull * R + k]; p.held[lo + k] = 1;
+  }
+  return KB_OK;
+}
+
+static int cs_dense(kb_sim* s, CsPart& p) {
+  (void)hipSetDevice(s->device);
+  const Dev& d = s->d;
+  if (!s->cs_buf) HIPCHK(talloc(s, &s->cs_buf, (size_t)s->W + 3ull * s->R + 3ull * d.NWR));
+  CsDense a;
+  // the masks sit right after known_by: both are whole KiB, so the masks' 16-byte loads are aligned for any R
+  a.kb = s->cs_buf; a.ab = a.kb + s->W; a.sb = a.ab + d.NWR; a.vb = a.sb + d.NWR; a.rowc = a.vb + d.NWR;
+  const uint32_t cb = s->W / CS_COLS;
+  // rows per wave: about 16 waves a CU (the loads in flight that a streaming pass needs), whole fold periods.
+  // env KB_CENSUS_RPW overrides it: a measurement knob only (tools/census_cost.py records its value, DESIGN.md
+  // §12); results do not depend on it
+  uint64_t rpw = ((uint64_t)s->R * cb + 16ull * s->ncu - 1) / (16ull * s->ncu);
+  if (const char* ev = getenv("KB_CENSUS_RPW")) rpw = (uint64_t)atoll(ev);
+  rpw = std::min<uint64_t>(std::max<uint64_t>((rpw + CS_FOLD - 1) / CS_FOLD * CS_FOLD, CS_FOLD), CS_MAX_RPW);
+  a.rpw = (uint32_t)rpw;
+  const uint32_t tiles = (uint32_t)((s->R + 4 * rpw - 1) / (4 * rpw));
+  CsTimer tm;
+  if (!tm.start(s->st)) { seterr("census: events"); return KB_IO_ERROR; }
+  HIPCHK(hipMemsetAsync(a.kb, 0, 4ull * ((size_t)s->W + 3ull * d.NWR + 3ull * s->R), s->st));
+  k_cs_masks<<<(d.NWR + 255) / 256, 256, 0, s->st>>>(d, a);
+  k_cs_dense<<<dim3(cb, tiles), 256, 0, s->st>>>(d, a);
+  tm.stop(s->st);
+  HIPCHK(hipGetLastError());
+  const int rc = cs_collect(p, s->C, s->lo, s->R, a.kb, a.rowc, d.alive, d.ext, s->st);
+  if (rc) return rc;
+  s->cs_ms = tm.ms(); p.ms += s->cs_ms;
+  return KB_OK;
+}
+
+static int cs_sparse(SpSim* S, CsPart& p) {
+  (void)hipSetDevice(S->device);
+  const SpDev& d = S->d;
+  const uint32_t C = S->C, R = S->R;
+  if (!S->cs_buf) {
+    if (sp_alloc(S, &S->cs_buf, 2ull * C + 3ull * R + 4) != hipSuccess) { seterr("census: device allocation failed"); return KB_CAPACITY; }
+  }
+  CsSparse a;
+  a.delta = reinterpret_cast<int32_t*>(S->cs_buf); a.acc = S->cs_buf + C; a.rowc = a.acc + 4; a.kb = a.rowc + 3ull * R;
+  CsTimer tm;
+  if (!tm.start(S->st)) { seterr("census: events"); return KB_IO_ERROR; }
+  HIPCHK(hipMemsetAsync(S->cs_buf, 0, 4ull * ((size_t)C + 4 + 3ull * R), S->st));
+  k_cs_sp_base<<<(C + 255) / 256, 256, 0, S->st>>>(d, a);
+  k_cs_sp_rows<<<(R + 255) / 256, 256, 0, S->st>>>(d, a);
+  k_cs_sp_finish<<<(C + 255) / 256, 256, 0, S->st>>>(d, a);
+  tm.stop(S->st);
+  HIPCHK(hipGetLastError());
+  const int rc = cs_collect(p, C, S->lo, R, a.kb, a.rowc, d.alive, d.ext, S->st);
+  if (rc) return rc;
+  S->cs_ms = tm.ms(); p.ms += S->cs_ms;
+  return KB_OK;
+}
+
+// the O(ids) reductions of the summary, on the host
+static void cs_summary(const CsPart& p, uint32_t C, int32_t round, kb_census* out, uint32_t* missing, uint32_t* stale) {
+  memset(out, 0, sizeof *out);
+  out->round = round;
+  uint32_t running = 0;
+  for (uint32_t j = 0; j < C; ++j) running += p.alive[j] != 0;
+  out->running = running;
+  for (uint32_t i = 0; i < C; ++i) {
+    const bool obs = p.held[i] && p.alive[i];
+    const uint32_t m = obs ? running - p.run[i] : 0u, st = obs ? p.stale[i] : 0u;
+    if (missing) missing[i] = m;
+    if (stale) stale[i] = st;
+    if (!obs) continue;
+    out->observers++; out->pairs += p.view[i]; out->missing += m; out->stale += st;
+    out->exact_views += m == 0 && st == 0;
+  }
+  out->least_known = out->top_ghost = KB_CENSUS_NONE;
+  for (uint32_t j = 0; j < C; ++j) {
+    const uint32_t k = p.kb[j];
+    if (p.alive[j]) {
+      out->full_ids += k == out->observers;
+      if (out->least_known == KB_CENSUS_NONE || k < out->least_known_by) { out->least_known = j; out->least_known_by = k; }
+    } else if (!p.ext[j] && k) {
+      out->ghost_ids++;
+      if (k > out->top_ghost_by) { out->top_ghost = j; out->top_ghost_by = k; }
+    }
+  }
+}
+
+extern "C" int kb_sim_census(kb_sim* s, kb_census* out, uint32_t* known_by, size_t cap_ids, uint32_t* missing,
+                             uint32_t* stale, size_t cap_rows) {
+  if (!s || !out) return KB_INVALID_ARGUMENT;
+  if ((known_by && cap_ids < s->C) || ((missing || stale) && cap_rows < s->C)) {
+    seterr("kb_sim_census: an output array is shorter than the capacity"); return KB_INVALID_ARGUMENT;
+  }
+  CsPart p;
+  cs_part_init(p, s->C);
+  int32_t round = 0;
+  if (is_group(s)) {
+    for (kb_sim* t : s->shards) { const int rc = t->sp ? cs_sparse(t->sp, p) : cs_dense(t, p); if (rc) return rc; }
+    round = s->shards[0]->sp ? s->shards[0]->sp->round : s->shards[0]->round;
+  } else {
+    const int rc = s->sp ? cs_sparse(s->sp, p) : cs_dense(s, p);
+    if (rc) return rc;
+    round = s->sp ? s->sp->round : s->round;
+  }
+  s->cs_ms = p.ms;
+  cs_summary(p, s->C, round, out, missing, stale);
+  if (known_by) memcpy(known_by, p.kb.data(), 4ull * s->C);
+  return KB_OK;
+}
+
+extern "C" int kb_sim_census_device_ms(kb_sim* s, double* ms) {
+  if (!s || !ms) return KB_INVALID_ARGUMENT;
+  *ms = s->cs_ms;
+  return KB_OK;
+}

@@ -416,6 +416,8 @@ struct kb_sim {
   uint64_t k_bytes0[NSTAT] = {};
   uint64_t host_syncs = 0;             // host waits on the device (stream syncs, pinned hand-offs) since creation
   uint32_t ncu = 256;
+  uint32_t* cs_buf = nullptr;          // the census's scratch (kb_census.h), allocated by the first census
+  double cs_ms = 0;                    // device time of the last census
   bool debug_waves = false;
   size_t lds_per_cu = 65536;
   // kb_sim_create_local: a façade over `world` in-process shards (one host thread each per step)
@@ -2481,3 +2483,6 @@ extern "C" int kb_sim_sparse_footprint(kb_sim* s, uint64_t* out, size_t cap) {
   if (!s->sp) { seterr("not a KB_VARIANT_SPARSE_ROWS handle"); return KB_INVALID_OPERATION; }
   return sp_footprint(s->sp, out, cap);
 }
+
+// ---- the view census (include/kaboodle_census.h) ----------------------------------------------------------
+#include "kb_census.h"

@@ -77,6 +77,8 @@ struct SpSim {
   uint64_t k_n[SPK_N] = {};
   double round_ms = 0; uint64_t round_n = 0;
   uint64_t host_syncs = 0;
+  uint32_t* cs_buf = nullptr;                       // the census's scratch (kb_census.h), allocated by the first census
+  double cs_ms = 0;                                 // device time of the last census
   // external peers
   std::vector<uint8_t> h_ext;
   size_t n_ext = 0;

@@ -2,10 +2,13 @@
 base, measured on the GPU at 64K peers (the scenario of tests/test_gpu_fullsize.py::test_partition_heal_64k:
 5 % loss, halves cut off for rounds 3-11, healed at round 12 by ping_addrs across the halves).
 
-For sampled rows at several rounds: membership exceptions against (a) one global base set (bitwise
-majority of the sampled rows) and (b) a per-partition base (majority of the rows of the same half); the
-entries whose stamp is not "ancient" (Known(t) inside the window, or WaitingFor*), which a base+exceptions
-form must also store per row.  Written to profiles/r03_partition_divergence.json.
+At several rounds, over the WHOLE mesh from the device-side census (Mesh.census()): the mean view
+size, the entries missing from and stale in the views, and the exceptions against one global base set (the ids a
+majority of all running rows hold: known_by * 2 > observers).  For sampled rows (the census has no per-row
+exception maximum, no per-partition base and no stamps): the exceptions against the sampled rows' majority and
+against a per-partition base (majority of the rows of the same half), and the entries whose stamp is not
+"ancient" (Known(t) inside the window, or WaitingFor*), which a base+exceptions form must also store per row.
+Written to profiles/r03_partition_divergence.json.
 
     python tools/partition_divergence.py [out.json]
 """
@@ -57,8 +60,18 @@ def measure(mode):
             fresh = ((allr > 2)).sum(1)               # Known(t) inside the stamp window (self included)
             susp = (allr == 1).sum(1)
             st = m.stats()
+            c = m.census()
+            obs = max(c.summary["observers"], 1)
+            kb = c.known_by.astype(np.int64)
+            base_all = kb * 2 > obs                   # the whole mesh's majority base
             e = {"round": mark, "agree_frac": round(st["agree"] / max(st["alive"], 1), 4),
-                 "view_size_mean": float(mem.sum(1).mean()),
+                 "view_size_mean": c.summary["pairs"] / obs,
+                 "whole_mesh": {"observers": c.summary["observers"], "exact_views": c.summary["exact_views"],
+                                "missing_mean": c.summary["missing"] / obs, "missing_max": int(c.missing.max()),
+                                "stale_mean": c.summary["stale"] / obs, "stale_max": int(c.stale.max()),
+                                "base_size": int(base_all.sum()),
+                                "exceptions_vs_global_base_mean": float(np.where(base_all, obs - kb, kb).sum() / obs)},
+                 "sampled_view_size_mean": float(mem.sum(1).mean()),
                  "exceptions_vs_global_base": {"mean": float(exc_g.mean()), "max": int(exc_g.max())},
                  "exceptions_vs_partition_base": {"mean": float(exc_p.mean()), "max": int(exc_p.max())},
                  "base_sizes": {"global": int(base_g.sum()), "half_a": int(base_a.sum()), "half_b": int(base_b.sum())},
