@@ -120,8 +120,12 @@ enum {
                                 every round (also env KB_WAVE_GRAPH=1)                  */
   KB_DBG_RESP_WAVE_HBM = 64u,/* Join responses by wave with the rows read in place (the path of rows too
                                 wide for a wave's LDS copy, > 110K ids)                                */
-  KB_DBG_NO_UNION = 128u     /* row shards: Join responses travel as their id lists, not as one union per
+  KB_DBG_NO_UNION = 128u,    /* row shards: Join responses travel as their id lists, not as one union per
                                 (source shard, joiner) (A/B and parity surface)          */
+  KB_DBG_A3X_KPL8 = 256u,    /* KB_VARIANT_EXACT_LRU: A3 by the kernel of 128K-512K-id rows (eight block bounds
+                                per lane) at any width                                                 */
+  KB_DBG_A3X_WIDE = 512u     /* KB_VARIANT_EXACT_LRU: A3 by the one-pass kernel of rows above 512K ids at any
+                                width (wins over KB_DBG_A3X_KPL8)                                      */
 };
 
 /* Per-peer state as reported by peer_states() (PeerState, src/structs.rs:27-41). */
@@ -311,10 +315,25 @@ int  kb_sim_dump_suspects(kb_sim* sim, uint32_t node, int32_t* out, size_t cap, 
    from HBM, 64 Join responses by wave, 128 KnownPeers BIG group in LDS, 256 Join responses by wave
    from the rows in place).  Test surface.                                                          */
 int  kb_sim_debug_paths(kb_sim* sim, uint32_t* mask);
-/* Development counters since creation: [A3 rows scanned, rows scanned past their first 1024 ids,
-   1024-id stamp chunks read] and, with cap >= 5, the row-shard exchange's bytes [sent to other shards,
-   sent to every shard] (records and payload; summed over an in-process group's shards; 0 unsharded).
-   Test surface.                                                                                     */
+/* Development counters since creation (cap >= 3; slots 3-4 with cap >= 5, slots 5-9 with cap >= 10; all
+   summed over an in-process group's shards; all 0 on sparse rows).  Test surface.
+     [0] A3 rows scanned (running peers x rounds)
+     [1] rows that read past their first 1024 ids
+     [2] 1024-id pieces of a row read
+   Slots 0-2 cover both A3 orders.  In the stamp-window order the row pass counts 1024-id stamp chunks
+   from the sweep front.  Under KB_VARIANT_EXACT_LRU the exact-order kernel counts the 1024-id blocks it
+   loads: [1] = rows that loaded more than one block, [2] = blocks loaded, with both passes of a redone
+   row and the row's blocks of a live-byte pass counted; the one-pass wide kernel counts every block of
+   the row.
+     [3] row-shard exchange: bytes sent to other shards (records and payload; 0 unsharded)
+     [4] row-shard exchange: bytes sent to every shard
+   The exits of the exact-order kernel, in rows (0 in the stamp-window order); a running row takes
+   exactly one of [5], [6], [7], [9]:
+     [5] answered from the 32-bit keys
+     [6] redone with 64-bit keys because the fifth key's offset from the first bound clamped at 255
+     [7] redone with 64-bit keys because fewer than five saturated entries exist
+     [8] took the pass over the live stamp bytes (follows [7])
+     [9] taken by the one-pass kernel of rows above 512K ids (or KB_DBG_A3X_WIDE)                      */
 int  kb_sim_debug_counters(kb_sim* sim, uint64_t* out, size_t cap);
 /* Canonical curious table: for each entry sorted by peer: peer, nobs, obs[0..3] (6 x int32).       */
 int  kb_sim_dump_curious(kb_sim* sim, uint32_t node, int32_t* out, size_t cap, size_t* n);

@@ -20,12 +20,16 @@ enum StatIdx {
   S_KPIDS,                        // peer entries of the KnownPeers messages sent (kb_stats.sent_kp_ids)
   S_ROWB,                         // bytes the row pass moved (bench roofline; not a kb_stats field)
   S_FOLDB,                        // member-bit bytes the fold read (bench roofline; not a kb_stats field)
-  S_A3ROWS, S_A3DEEP, S_A3CHUNKS,  // A3 scans: rows, rows past their first chunk, chunks read (kb_sim_debug_counters)
+  S_A3ROWS, S_A3DEEP, S_A3CHUNKS,  // A3 scans, either order: rows, rows past their first 1024 ids (exact order: first
+                                  // block loaded), 1024-id chunks / blocks read (kb_sim_debug_counters)
   S_ALIVER,                       // running peers summed over the rounds (kb_stats.alive_rounds; counted by shard 0)
   S_RESPB,                        // bytes k_resp_wave moved (bench; not a kb_stats field)
   S_PROCB,                        // bytes k_proc moved (bench; not a kb_stats field)
   S_PROBERESP,                    // ProbeResponses sent (kb_stats.probe_responses)
   S_EXPORT,                       // records routed to external peers (kb_stats.exported)
+  S_A3X32, S_A3XCLAMP, S_A3XFEW, S_A3XLIVE, S_A3XWIDE,   // k_a3_exact's exits, rows: answered from 32-bit keys, redone
+                                  // for a clamped fifth key, redone with fewer than five saturated, + the live-byte
+                                  // pass, taken by the one-pass wide kernel (kb_sim_debug_counters[5..9]; contiguous)
   NSTAT
 };
 enum CtrIdx {

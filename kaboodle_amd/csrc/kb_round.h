@@ -223,9 +223,12 @@ __device__ __attribute__((always_inline)) inline void write_a3_keys(uint32_t* pa
 // item (a converged start's five ancient candidates sit in the sweep front's block: one scan and one top-five per row,
 // whose minima are also the answer).  KPL: block bounds per lane, the row's 1024-id blocks over 64 lanes (2 up to
 // 128K ids, 8 up to 512K): the bound selection is a quarter of the instructions at 64K rows with KPL 2.
+// Returns the row's counts for kb_sim_debug_counters, wave-uniform: A3X_* exit bits << 24 | blocks loaded (both passes
+// of a redo and the live-byte pass included); 0 for a row that is not running.
+enum : uint32_t { A3X_K32 = 1u, A3X_CLAMP = 2u, A3X_FEW = 4u, A3X_LIVE = 8u, A3X_WIDE = 16u };
 template <uint32_t KPL>
-__device__ __attribute__((always_inline)) inline void a3x_narrow(const Dev& d, uint32_t* part, int32_t r, uint32_t i,
-                                                                 uint32_t cur, bool alive) {
+__device__ __attribute__((always_inline)) inline uint32_t a3x_narrow(const Dev& d, uint32_t* part, int32_t r, uint32_t i,
+                                                                     uint32_t cur, bool alive) {
   const uint32_t l = lane(), C = d.C, NB = d.W >> 10;
   int32_t* lbrow = d.tlb + (size_t)i * NB;
   int32_t lbk[KPL];
@@ -234,11 +237,12 @@ __device__ __attribute__((always_inline)) inline void a3x_narrow(const Dev& d, u
     const uint32_t b = l + 64 * k;
     lbk[k] = (b < NB && (b << 10) < C) ? lbrow[b] : INT32_MAX;        // INT32_MAX: nothing saturated (or no ids)
   }
-  if (!alive) return;
+  if (!alive) return 0u;
   const uint8_t* srow = row_of(d, i);
   const uint32_t* brow = bits_of(d, i);
   const int32_t* trow = d.tst + (size_t)i * d.W;
   const uint32_t p = cur + 1 == C ? 0 : cur + 1;                     // the sweep front: rotated id 0
+  uint32_t cnt = 0;                                                  // blocks loaded; the exit bits at the exits
   uint32_t rkey[KPL];                                                // the block's smallest rotated id
 #pragma unroll
   for (uint32_t k = 0; k < KPL; ++k) {
@@ -269,14 +273,16 @@ __device__ __attribute__((always_inline)) inline void a3x_narrow(const Dev& d, u
       smin = (int32_t)(wave_min((uint32_t)smin ^ 0x80000000u) ^ 0x80000000u);   // signed minimum
       if (l == 0) lbrow[b] = smin;                                   // exact now
       wave_top5_32(top, m5);
+      ++cnt;
     }
     if (!redo && m5[4] != ~0u) {                                     // the last step's five: no scan after it
       uint32_t o = 0xFFFFFFFFu;
 #pragma unroll
       for (uint32_t k = 0; k < 5; ++k) if (l == k) o = (k << 24) | (m5[k] & 0xFFFFFFu);
       if (l < 10) part[(size_t)i * 10 + l] = o;
-      return;
+      return cnt | (A3X_K32 << 24);
     }
+    cnt |= (redo ? A3X_CLAMP : A3X_FEW) << 24;
   }
   // 64-bit keys: instants 255 or more above the first bound among the five, or fewer than five saturated (then the
   // live bytes too).  The bounds the pass above made exact stay valid; every block is a candidate again.
@@ -302,12 +308,15 @@ __device__ __attribute__((always_inline)) inline void a3x_narrow(const Dev& d, u
     smin = (int32_t)(wave_min((uint32_t)smin ^ 0x80000000u) ^ 0x80000000u);
     if (l == 0) lbrow[b] = smin;
     wave_top5(top, m5);
+    ++cnt;
   }
   if (m5[4] == ~0ull) {                                              // fewer than five saturated: + the live bytes
     for (uint32_t b = 0; b < NB; ++b) a3x_block<false, true>(d, i, b, cur, E, srow, brow, trow, top);
     wave_top5(top, m5);
+    cnt += NB | (A3X_LIVE << 24);
   }
   write_a3_keys(part, i, l, m5);
+  return cnt;
 }
 // One kernel per row width (the host picks by NB = W / 1024): each holds only its own path, so the 64K rows' KPL-2
 // kernel is not sized for the wider paths' registers (74 VGPRs, 6 waves per SIMD, instead of 105 and 4): beside the
@@ -315,23 +324,44 @@ __device__ __attribute__((always_inline)) inline void a3x_narrow(const Dev& d, u
 template <uint32_t KPL>
 __global__ __launch_bounds__(256) void k_a3_exact(Dev d, uint32_t* part, int32_t r) {
   const uint32_t i = d.lo + blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= d.hi) return;
-  const uint32_t cur = d.a3cur[i];
-  const bool alive = d.alive[i] != 0;
-  if constexpr (KPL != 0) {
-    a3x_narrow<KPL>(d, part, r, i, cur, alive);
-  } else {
-    if (!alive) return;                                              // wider rows: one pass over everything
-    const uint32_t NB = d.W >> 10;
-    unsigned long long top[5] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
-    const int32_t E = epoch_base(r);
-    for (uint32_t b = 0; b < NB; ++b) a3x_block<true, true>(d, i, b, cur, E, row_of(d, i), bits_of(d, i), d.tst + (size_t)i * d.W, top);
-    unsigned long long m5[5];
-    wave_top5(top, m5);
-    write_a3_keys(part, i, lane(), m5);
+  uint32_t cnt = 0;                                                  // the row's counts (a3x_narrow), wave-uniform
+  if (i < d.hi) {
+    const uint32_t cur = d.a3cur[i];
+    const bool alive = d.alive[i] != 0;
+    if constexpr (KPL != 0) {
+      cnt = a3x_narrow<KPL>(d, part, r, i, cur, alive);
+    } else if (alive) {                                              // wider rows: one pass over everything
+      const uint32_t NB = d.W >> 10;
+      unsigned long long top[5] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
+      const int32_t E = epoch_base(r);
+      for (uint32_t b = 0; b < NB; ++b) a3x_block<true, true>(d, i, b, cur, E, row_of(d, i), bits_of(d, i), d.tst + (size_t)i * d.W, top);
+      unsigned long long m5[5];
+      wave_top5(top, m5);
+      write_a3_keys(part, i, lane(), m5);
+      cnt = NB | (A3X_WIDE << 24);
+    }
+  }
+  // the counts of the workgroup's four rows are summed in LDS and added once per workgroup and counter, as k_fold
+  // adds S_FOLDB: rows, rows that loaded more than one block, blocks, then one counter per exit bit
+  __shared__ uint32_t s_cnt[4];
+  if (lane() == 0) s_cnt[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x < 8) {
+    const uint32_t k = threadIdx.x;
+    uint32_t t = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 4; ++w) {
+      const uint32_t c = s_cnt[w], nb = c & 0xFFFFFFu;
+      t += k == 0 ? (c != 0) : k == 1 ? (nb > 1) : k == 2 ? nb : ((c >> (24 + (k - 3))) & 1u);
+    }
+    const int idx[8] = {S_A3ROWS, S_A3DEEP, S_A3CHUNKS, S_A3X32, S_A3XCLAMP, S_A3XFEW, S_A3XLIVE, S_A3XWIDE};
+    if (t) slot_add(d, idx[k], t);
   }
 }
-__host__ __device__ inline uint32_t a3_kpl(uint32_t W) {               // 0: the wide path
+// the kernel's width: KB_DBG_A3X_WIDE / KB_DBG_A3X_KPL8 force the one-pass kernel / the KPL-8 kernel at any width
+__host__ __device__ inline uint32_t a3_kpl(uint32_t W, uint32_t dbg = 0) {   // 0: the wide path
+  if (dbg & KB_DBG_A3X_WIDE) return 0u;
+  if (dbg & KB_DBG_A3X_KPL8) return A3X_KPL;
   const uint32_t NB = W >> 10;
   return NB <= 64 * 2 ? 2u : NB <= 64 * A3X_KPL ? A3X_KPL : 0u;
 }

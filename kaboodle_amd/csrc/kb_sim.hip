@@ -1488,7 +1488,7 @@ static int step_round(kb_sim* s) {
   // write checkpoints and fingerprints only
   if (d.tst) {
     side_fork(s, 2);
-    const uint32_t kpl = a3_kpl(s->W);
+    const uint32_t kpl = a3_kpl(s->W, d.dbg);
     if (kpl == 2) klaunch_on(s, s->st2, KI_A3_EXACT, k_a3_exact<2>, dim3((R + 3) / 4), dim3(256), 0, d, s->ro.part, r);
     else if (kpl) klaunch_on(s, s->st2, KI_A3_EXACT, k_a3_exact<A3X_KPL>, dim3((R + 3) / 4), dim3(256), 0, d, s->ro.part, r);
     else klaunch_on(s, s->st2, KI_A3_EXACT, k_a3_exact<0>, dim3((R + 3) / 4), dim3(256), 0, d, s->ro.part, r);
@@ -2450,20 +2450,25 @@ extern "C" int kb_sim_debug_paths(kb_sim* s, uint32_t* mask) {
   HIPCHK(hipMemcpy(mask, s->d.ctr + C_PATHS, 4, hipMemcpyDeviceToHost));
   return KB_OK;
 }
-// development counters (test surface): [A3 rows scanned, rows scanned past their first chunk, chunks read]
+// development counters (test surface; include/kaboodle_sim.h): the A3 scan's [0..2], the row-shard exchange's bytes
+// [3..4], k_a3_exact's exits [5..9]; an in-process group's are summed over its shards
 extern "C" int kb_sim_debug_counters(kb_sim* s, uint64_t* out, size_t cap) {
-  if (s && s->sp) { if (!out || cap < 3) return KB_INVALID_ARGUMENT; out[0] = out[1] = out[2] = 0; return KB_OK; }
+  if (s && s->sp) { if (!out || cap < 3) return KB_INVALID_ARGUMENT; for (size_t k = 0; k < cap && k < 10; ++k) out[k] = 0; return KB_OK; }
   SPG_FIRST([&](kb_sim* t) { return kb_sim_debug_counters(t, out, cap); });
   if (!s || !out || cap < 3) return KB_INVALID_ARGUMENT;
-  kb_sim* h = is_group(s) ? s->shards[0] : s;
-  { const int rc = fold_stats(h); if (rc) return rc; }
-  unsigned long long v[3];
-  HIPCHK(hipMemcpy(v, h->d.stats + S_A3ROWS, sizeof v, hipMemcpyDeviceToHost));
-  for (int k = 0; k < 3; ++k) out[k] = v[k];
-  if (cap >= 5) {                                    // the row-shard exchange's bytes (sharded meshes; 0 otherwise)
-    out[3] = out[4] = 0;
-    if (is_group(s)) for (kb_sim* t : s->shards) { out[3] += t->xbytes_cross; out[4] += t->xbytes_all; }
-    else { out[3] = s->xbytes_cross; out[4] = s->xbytes_all; }
+  { const int rc = fold_stats(s); if (rc) return rc; }
+  static_assert(S_A3CHUNKS == S_A3ROWS + 2 && S_A3XWIDE == S_A3X32 + 4, "the A3 counters are read as two blocks");
+  const size_t n = cap >= 10 ? 10 : cap >= 5 ? 5 : 3;
+  for (size_t k = 0; k < n; ++k) out[k] = 0;
+  std::vector<kb_sim*> one{s};
+  for (kb_sim* t : is_group(s) ? s->shards : one) {
+    unsigned long long v[3], x[5];
+    HIPCHK(hipMemcpy(v, t->d.stats + S_A3ROWS, sizeof v, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; ++k) out[k] += v[k];
+    if (n >= 5) { out[3] += t->xbytes_cross; out[4] += t->xbytes_all; }   // 0 unsharded
+    if (n < 10) continue;
+    HIPCHK(hipMemcpy(x, t->d.stats + S_A3X32, sizeof x, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 5; ++k) out[5 + k] += x[k];
   }
   return KB_OK;
 }

@@ -105,12 +105,14 @@ def with_cfg(case: dict, **kw) -> dict:
 
 
 def run_case(case: dict, rounds: int, check_every: int = 1, full_rows: bool = True, verbose: bool = False,
-             shards: int = 0, gpu: Sim | None = None, peer_states: bool = False):
+             shards: int = 0, gpu: Sim | None = None, peer_states: bool = False, omp: bool = False, on_round=None):
     """Run `case` on both implementations; returns (ok, message, final gpu stats).  shards=k runs the
     GPU mesh as k row shards exchanging every wave (kb_sim_create_local); `gpu` = an already created
-    GPU handle for the case (e.g. an RCCL rank); peer_states: also compare peer_states() of every node."""
+    GPU handle for the case (e.g. an RCCL rank); peer_states: also compare peer_states() of every node;
+    omp: the OpenMP build of the oracle (the same results, for capacities in the thousands);
+    on_round(r, oracle, gpu): called after every round's step, before the comparison (e.g. to read counters)."""
     cfg = case["cfg"]
-    o = Sim(oracle_lib(), cfg)
+    o = Sim(oracle_lib(omp), cfg)
     g = gpu if gpu is not None else Sim(gpu_lib(), cfg, shards=shards)
     setup(o, case)
     setup(g, case)
@@ -118,6 +120,8 @@ def run_case(case: dict, rounds: int, check_every: int = 1, full_rows: bool = Tr
         apply_events((o, g), case, r)
         o.step(1)
         g.step(1)
+        if on_round is not None:
+            on_round(r, o, g)
         if (r + 1) % check_every == 0 or r == rounds - 1:
             d = diff_states(state_of(o, full_rows), state_of(g, full_rows))
             if not d and peer_states:

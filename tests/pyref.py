@@ -116,8 +116,9 @@ class Peer:
 
 class PyMesh:
     def __init__(self, capacity, initial_nodes, converged=False, seed=1, loss=0.0, churn=0.0, fault_end=-1,
-                 max_waves=8, failed_honoured=True, id_len=0, partition=None):
+                 max_waves=8, failed_honoured=True, id_len=0, partition=None, exact_lru=False):
         self.C = capacity
+        self.exact_lru = exact_lru      # KB_VARIANT_EXACT_LRU: A3 sorts by the instant itself, not by its stamp byte
         self.k0, self.k1 = seed & MASK, (seed >> 32) & MASK
         self.loss_thr = min(int(round(loss * 2 ** 32)), MASK)
         self.churn_thr = min(int(round(churn * 2 ** 32)), MASK)
@@ -394,7 +395,10 @@ class PyMesh:
             self.stats["removed_timeout"] += 1
         # ping_random_peer :655-703
         c = [q for q, (st, _, _) in p.known.items() if st == KNOWN and q != p.id]
-        c.sort(key=lambda q: (stamp_key(p.known[q][1], r), (q - p.a3cur - 1) % self.C))
+        # by last contact, oldest first (:662-675): the instant itself (exact_lru; the converged start's entries share
+        # one instant and tie) or its byte in the declared stamp window; ties in rotated id order from the sweep front
+        age = (lambda q: p.known[q][1]) if self.exact_lru else (lambda q: stamp_key(p.known[q][1], r))
+        c.sort(key=lambda q: (age(q), (q - p.a3cur - 1) % self.C))
         c = c[:NUM_CANDIDATES]
         if c:
             t = c[mulhi(self.ph(p.id, r, P_PING << 24, 0)[0], len(c))]

@@ -10,7 +10,7 @@ import zlib
 
 import numpy as np
 
-from kaboodle_amd._ffi import KB_FAILED_SOCKET_FAITHFUL, KB_INIT_CONVERGED, Sim, SimConfig
+from kaboodle_amd._ffi import KB_FAILED_SOCKET_FAITHFUL, KB_INIT_CONVERGED, KB_VARIANT_EXACT_LRU, Sim, SimConfig
 
 CONFIG1_IDS = [b"top-left", b"top-right", b"bottom-left", b"bottom-right"]   # 2x2-layout.kdl:6-20
 
@@ -66,7 +66,8 @@ def pymesh_of(sc):
     part = (c.partition_groups, c.partition_start, c.partition_end) if c.partition_groups else None
     pm = pyref.PyMesh(c.capacity, c.initial_nodes, converged=c.init_mode == KB_INIT_CONVERGED, seed=c.seed,
                       loss=c.loss, churn=c.churn, fault_end=c.fault_end_round, max_waves=c.max_waves,
-                      failed_honoured=c.failed_mode != KB_FAILED_SOCKET_FAITHFUL, id_len=c.id_len, partition=part)
+                      failed_honoured=c.failed_mode != KB_FAILED_SOCKET_FAITHFUL, id_len=c.id_len, partition=part,
+                      exact_lru=c.variant == KB_VARIANT_EXACT_LRU)
     return pm
 
 

@@ -67,8 +67,16 @@ def test_parity_exact_lru_block_bounds(gpu):
                              seed=41, variant=KB_VARIANT_EXACT_LRU),
             "events": {70: [("stop", 17, None)], 75: [("restart", 17, None)], 150: [("stop", 2900, None)],
                        160: [("restart", 2900, None)]}}
-    ok, msg, _ = parity.run_case(case, 200, check_every=4, full_rows=True)
+    import ctypes as C
+    g = Sim(gpu, case["cfg"])
+    ok, msg, _ = parity.run_case(case, 200, check_every=4, full_rows=True, gpu=g)
     assert ok, f"exact LRU blocks: {msg}"
+    # every exit of the narrow kernel was taken (kb_sim_debug_counters: rows answered from the 32-bit keys, redone
+    # for the clamped fifth key, redone with fewer than five saturated entries: the churn joiners' rows)
+    buf = (C.c_uint64 * 10)()
+    assert gpu.lib.kb_sim_debug_counters(g.h, buf, 10) == 0
+    g.close()
+    assert buf[5] > 0 and buf[6] > 0 and buf[7] > 0, list(buf)
 
 
 EXT_CASES = ["converged_loss_256", "churn_loss_512", "partition_heal", "stop_start", "join_64"]
