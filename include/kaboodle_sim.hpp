@@ -12,6 +12,7 @@
 
 #include "kaboodle_sim.h"
 #include "kaboodle_census.h"
+#include "kaboodle_reciprocity.h"
 
 namespace kb {
 
@@ -57,6 +58,21 @@ class Mesh {
                         arrays ? c.missing.data() : nullptr, arrays ? c.stale.data() : nullptr, c.missing.size()),
           "kb_sim_census");
     return c;
+  }
+
+  // the reciprocity census (kaboodle_reciprocity.h; HIP library only): one-way and mutual gaps between views.
+  // pairs: the mutual pairs (i, j), i < j, ascending, two words each; empty when their number is above max_pairs
+  // (summary.mutual_pairs has the total).  arrays = false asks for the summary alone.
+  struct Reciprocity { kb_reciprocity summary; std::vector<uint32_t> mutual, lacks, lacked_by, pairs; };
+  Reciprocity reciprocity(bool arrays = true, size_t max_pairs = 65536) const {
+    Reciprocity r;
+    if (arrays) { r.mutual.resize(capacity_); r.lacks.resize(capacity_); r.lacked_by.resize(capacity_); r.pairs.resize(2 * max_pairs); }
+    check(kb_sim_reciprocity(h_, &r.summary, arrays ? r.mutual.data() : nullptr, arrays ? r.lacks.data() : nullptr,
+                             arrays ? r.lacked_by.data() : nullptr, r.mutual.size(),
+                             arrays && max_pairs ? r.pairs.data() : nullptr, arrays ? max_pairs : 0),
+          "kb_sim_reciprocity");
+    r.pairs.resize(2 * (size_t)r.summary.pairs_listed);
+    return r;
   }
 
   // the per-instance view: method names of src/lib.rs

@@ -90,6 +90,17 @@ class KbCensus(C.Structure):
 KB_CENSUS_NONE = 0xFFFFFFFF
 
 
+class KbReciprocity(C.Structure):
+    """kb_reciprocity (include/kaboodle_reciprocity.h)."""
+    _fields_ = [("round", C.c_int32), ("observers", C.c_uint32), ("mutual_pairs", C.c_uint64),
+                ("oneway_pairs", C.c_uint64), ("rows_mutual", C.c_uint32), ("rows_oneway", C.c_uint32),
+                ("max_mutual_row", C.c_uint32), ("max_mutual", C.c_uint32), ("pairs_listed", C.c_uint64),
+                ("reserved", C.c_uint64 * 4)]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 class KbWireAddrC(C.Structure):
     _fields_ = [("ip", C.c_uint8 * 4), ("port", C.c_uint16), ("pad", C.c_uint16)]
 
@@ -226,6 +237,11 @@ _OPTIONAL = {
     "sim_census": (C.c_int, [C.c_void_p, C.POINTER(KbCensus), C.POINTER(C.c_uint32), C.c_size_t,
                              C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t]),
     "sim_census_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    # the reciprocity census (include/kaboodle_reciprocity.h; HIP library only, the oracle answers through
+    # reciprocity.reciprocity_ref)
+    "sim_reciprocity": (C.c_int, [C.c_void_p, C.POINTER(KbReciprocity), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                  C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t]),
+    "sim_reciprocity_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
 }
 
 
@@ -492,6 +508,34 @@ class Sim:
         """Device time of the last census() in ms (kb_sim_census_device_ms; HIP library only)."""
         v = C.c_double()
         self.lib.call("sim_census_device_ms", self.h, C.byref(v))
+        return v.value
+
+    def reciprocity(self, arrays: bool = True, max_pairs: int = 65536):
+        """The reciprocity census (include/kaboodle_reciprocity.h): a `Reciprocity` with `summary` (dict of
+        kb_reciprocity), the uint32 arrays `mutual`, `lacks`, `lacked_by` over all ids and `pairs`, the mutual
+        pairs (i, j), i < j, ascending, as an [n, 2] array (empty when their number is above max_pairs: the
+        summary's mutual_pairs has the total).  arrays=False: the summary alone, nothing listed.  Computed on the
+        device by kb_sim_reciprocity; a library without it (the CPU oracle) answers the same call through
+        reciprocity.reciprocity_ref, so both are compared through identical calls."""
+        from .reciprocity import Reciprocity, reciprocity_ref
+        if "sim_reciprocity" not in self.lib.fn:
+            return reciprocity_ref(self, max_pairs, arrays)
+        import numpy as np
+        out = KbReciprocity()
+        if not arrays:
+            self.lib.call("sim_reciprocity", self.h, C.byref(out), None, None, None, 0, None, 0)
+            return Reciprocity(out.as_dict(), None, None, None, None)
+        mu, lk, lb = (np.zeros(self.capacity, dtype=np.uint32) for _ in range(3))
+        pairs = np.zeros((max(max_pairs, 1), 2), dtype=np.uint32)
+        ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        self.lib.call("sim_reciprocity", self.h, C.byref(out), ptr(mu), ptr(lk), ptr(lb), self.capacity, ptr(pairs),
+                      max_pairs)
+        return Reciprocity(out.as_dict(), mu, lk, lb, pairs[: out.pairs_listed].copy())
+
+    def reciprocity_device_ms(self) -> float:
+        """Device time of the last reciprocity() in ms (kb_sim_reciprocity_device_ms; HIP library only)."""
+        v = C.c_double()
+        self.lib.call("sim_reciprocity_device_ms", self.h, C.byref(v))
         return v.value
 
     def row(self, node: int):

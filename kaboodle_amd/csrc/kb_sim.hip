@@ -418,6 +418,9 @@ struct kb_sim {
   uint32_t ncu = 256;
   uint32_t* cs_buf = nullptr;          // the census's scratch (kb_census.h), allocated by the first census
   double cs_ms = 0;                    // device time of the last census
+  uint32_t* rc_buf = nullptr;          // the reciprocity census's scratch (kb_recip.h), allocated by its first call
+  uint32_t* rc_pairs = nullptr; uint64_t rc_pairs_cap = 0;   // its pair list (entries), grown on demand
+  double rc_ms = 0;                    // device time of the last reciprocity census
   bool debug_waves = false;
   size_t lds_per_cu = 65536;
   // kb_sim_create_local: a façade over `world` in-process shards (one host thread each per step)
@@ -602,7 +605,7 @@ static void free_all(kb_sim* s) {
   for (void* p : s->allocs) (void)hipFree(p);
   s->allocs.clear();
   void* dyn[] = {s->newmask_base, s->respmask_base, s->resp_scratch, s->d_events, s->rmsg, s->rpay, s->rstatus,
-                 s->rinbox, s->rkp, s->d_presp, s->d_presp_n, s->rpack, s->rpack_in, s->d_inj, s->d_inj_ids};
+                 s->rinbox, s->rkp, s->d_presp, s->d_presp_n, s->rpack, s->rpack_in, s->d_inj, s->d_inj_ids, s->rc_pairs};
   for (void* p : dyn) if (p) (void)hipFree(p);
 }
 static void destroy_shard(kb_sim* s) {
@@ -2491,3 +2494,6 @@ extern "C" int kb_sim_sparse_footprint(kb_sim* s, uint64_t* out, size_t cap) {
 
 // ---- the view census (include/kaboodle_census.h) ----------------------------------------------------------
 #include "kb_census.h"
+
+// ---- the reciprocity census (include/kaboodle_reciprocity.h) ---------------------------------------------
+#include "kb_recip.h"

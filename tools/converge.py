@@ -9,6 +9,12 @@ no churn) on the GPU until every live peer's fingerprint equals the fingerprint 
 records the agreement and the mean view-size gap |known_i| - live into the trajectory and prints a
 progress line.  `--mode sock` = failed_mode socket_faithful (Failed never honoured, as over real
 sockets: src/networking.rs:44-55); `sim` = sim_sender (honoured).
+
+A run that ends without agreement (the cap or the budget), or any run with --reciprocity, records the reciprocity
+census of its last state (include/kaboodle_reciprocity.h) in the result: the summary and, when it
+fits --max-pairs, the list of mutual pairs — the gaps that can never heal — in place of the eight hand-sampled
+views earlier records carry, and beside it the view census's summary, which keeps what those
+views also showed: the stale entries and the ghosts (non-running ids some view still holds).
 """
 from __future__ import annotations
 
@@ -46,6 +52,9 @@ def main() -> int:
     ap.add_argument("--lru", choices=("window", "exact"), default="window",
                     help="A3's order: the 1-byte stamp window with the sweep front (declared), or the exact instants "
                          "(KB_VARIANT_EXACT_LRU, src/kaboodle.rs:662-675)")
+    ap.add_argument("--reciprocity", action="store_true",
+                    help="record the reciprocity census of the last state even when the run converged")
+    ap.add_argument("--max-pairs", type=int, default=65536, help="mutual pairs listed in the result at most")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import numpy as np
@@ -93,28 +102,25 @@ def main() -> int:
                       f"mean view gap {traj[-1]['view_gap_mean']}, {time.time() - t0:.0f} s", flush=True)
         if conv is None:
             sample(m, r - 1)
-            # the few nodes still disagreeing: what their views lack or keep
-            sc = m.scalars()
-            live = np.nonzero(sc[:, 0] != 0)[0]
-            lset = set(int(x) for x in live)
-            tfp = m.true_fingerprint() if hasattr(m, "true_fingerprint") else None
-            fps = m.fingerprints()
-            bad = [int(i) for i in live if tfp is not None and fps[i] != tfp][:8]
-            for i in bad:
-                ids = set(m.peers(i)) if hasattr(m, "peers") else set()
-                extra, missing = sorted(ids - lset)[:10], sorted(lset - ids)[:10]
-                st = [e for e in m.peer_states(i) if e[0] in extra][:10] if hasattr(m, "peer_states") else []
-                print(f"[converge {a.mode}] node {i} disagrees: extra {extra} missing {missing} extra states {st}", flush=True)
-                traj.append({"round": r - 1, "node": i, "extra": extra, "missing": missing})
+        recip = None
+        if conv is None or a.reciprocity:
+            # what is left: how much of the disagreement is permanent (mutual gaps never heal) and
+            # between which pairs
+            rc = m.reciprocity(max_pairs=a.max_pairs)
+            recip = {"summary": rc.summary, "census": m.census(arrays=False).summary, "mutual_pairs": rc.pairs.tolist(),
+                     "rows_lacked_by": int((rc.lacked_by > 0).sum()), "device_ms": round(m.reciprocity_device_ms(), 4)}
+            print(f"[converge {a.mode}] reciprocity: {json.dumps(rc.summary)}", flush=True)
+            print(f"[converge {a.mode}] census: {json.dumps(recip['census'])}", flush=True)
     out = {"workload": f"configs[2]: {n} peers, converged start, 1% loss, 0.1%/round churn, faults until round {F}",
            "failed_mode": "socket_faithful" if a.mode == "sock" else "sim_sender", "fault_end_round": F,
            "a3_order": a.lru,
            "converged_round": conv, "tail_rounds_to_converge": None if conv is None else conv - F + 1,
            "tail_rounds_run": traj[-1]["round"] - F + 1, "cap_rounds": cap,
            "stopped_by": "converged" if conv is not None else ("cap" if traj[-1]["round"] >= F + cap - 1 else "budget"),
-           "wall_s": round(time.time() - t0, 1), "lib_sha16": lib_sha16(), "lib_src_sha16": kb_src_sha16(), "trajectory": traj}
+           "wall_s": round(time.time() - t0, 1), "lib_sha16": lib_sha16(), "lib_src_sha16": kb_src_sha16(), "reciprocity": recip,
+           "trajectory": traj}
     txt = json.dumps(out)
-    print(json.dumps({k: v for k, v in out.items() if k != "trajectory"}), flush=True)
+    print(json.dumps({k: v for k, v in out.items() if k not in ("trajectory", "reciprocity")}), flush=True)
     if a.out:
         with open(a.out, "w") as f:
             f.write(txt)
