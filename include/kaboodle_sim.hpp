@@ -13,6 +13,7 @@
 #include "kaboodle_sim.h"
 #include "kaboodle_census.h"
 #include "kaboodle_reciprocity.h"
+#include "kaboodle_classes.h"
 
 namespace kb {
 
@@ -72,6 +73,23 @@ class Mesh {
                              arrays && max_pairs ? r.pairs.data() : nullptr, arrays ? max_pairs : 0),
           "kb_sim_reciprocity");
     r.pairs.resize(2 * (size_t)r.summary.pairs_listed);
+    return r;
+  }
+
+  // the fingerprint-class census (kaboodle_classes.h; HIP library only): the running rows grouped by equal
+  // fingerprint.  classes: the first `top` <= KB_FPC_LIST_MAX classes, size descending then fp ascending; rep / size:
+  // per id, the lowest id and the size of its class (KB_CENSUS_NONE / 0 for rows that are not running).
+  // arrays = false asks for the summary and the list alone.
+  struct FpClasses { kb_fp_classes summary; std::vector<kb_fp_class> classes; std::vector<uint32_t> rep, size; };
+  FpClasses fp_classes(size_t top = 16, bool arrays = true) const {
+    FpClasses r;
+    r.classes.resize(top);
+    if (arrays) { r.rep.resize(capacity_); r.size.resize(capacity_); }
+    size_t n = 0;
+    check(kb_sim_fp_classes(h_, &r.summary, top ? r.classes.data() : nullptr, top, &n, arrays ? r.rep.data() : nullptr,
+                            arrays ? r.size.data() : nullptr, r.rep.size()),
+          "kb_sim_fp_classes");
+    r.classes.resize(n);
     return r;
   }
 

@@ -94,6 +94,20 @@ class Mesh(Sim):
                 subs[k] = [c for c in subs[k] if not c.closed]
 
 
+    def fp_classes(self, top: int = 16, arrays: bool = True):
+        """Which camps the views fall into (include/kaboodle_classes.h): the running rows grouped
+        by equal fingerprint on the GPU.  Returns a `classes.FpClasses`: the summary (classes, largest,
+        singletons, the true class's size and rank, the size histogram), the `top` largest classes as (fp, size,
+        rep) and per id the representative and size of its class.  Rank shards raise KbError: a class spans ranks."""
+        return super().fp_classes(top, arrays)
+
+
+def fp_classes_of(fps, running, true_fp: int, top: int = 16, arrays: bool = True, device: int = 0):
+    """The class census's GPU kernels over host arrays (kb_fp_classes_of, a test surface): `classes.FpClasses`."""
+    from ._ffi import fp_classes_of as _of
+    return _of(lib(), fps, running, true_fp, top, arrays, device)
+
+
 def discover_mesh_member(mesh: "Mesh", prober=("192.0.2.1", 40000), max_rounds: int = 64):
     """Kaboodle::discover_mesh_member (src/lib.rs, src/discovery.rs:30-89) against a simulated mesh: broadcast
     Probe(prober), wait for a ProbeResponse, re-broadcast with the reference's back-off (1 s, x1.25, at most

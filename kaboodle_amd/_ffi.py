@@ -101,6 +101,29 @@ class KbReciprocity(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
 
 
+class KbFpClass(C.Structure):
+    """kb_fp_class (include/kaboodle_classes.h)."""
+    _fields_ = [("fp", C.c_uint32), ("size", C.c_uint32), ("rep", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class KbFpClasses(C.Structure):
+    """kb_fp_classes (include/kaboodle_classes.h)."""
+    _fields_ = [("round", C.c_int32), ("observers", C.c_uint32), ("classes", C.c_uint32), ("largest", C.c_uint32),
+                ("singletons", C.c_uint32), ("true_fp", C.c_uint32), ("true_size", C.c_uint32),
+                ("true_rank", C.c_uint32), ("size_hist", C.c_uint32 * 32), ("listed", C.c_uint32),
+                ("listed_observers", C.c_uint32), ("reserved", C.c_uint64 * 4)]
+
+    def as_dict(self) -> dict:
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n not in ("reserved", "size_hist")}
+        d["size_hist"] = [int(x) for x in self.size_hist]
+        return d
+
+
+KB_FPC_LIST_MAX = 1024
+_FPC_OUT = [C.POINTER(KbFpClasses), C.POINTER(KbFpClass), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32),
+            C.POINTER(C.c_uint32), C.c_size_t]
+
+
 class KbWireAddrC(C.Structure):
     _fields_ = [("ip", C.c_uint8 * 4), ("port", C.c_uint16), ("pad", C.c_uint16)]
 
@@ -242,6 +265,11 @@ _OPTIONAL = {
     "sim_reciprocity": (C.c_int, [C.c_void_p, C.POINTER(KbReciprocity), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                   C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t]),
     "sim_reciprocity_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    # the fingerprint-class census (include/kaboodle_classes.h; HIP library only, the oracle answers through
+    # classes.fp_classes_ref)
+    "sim_fp_classes": (C.c_int, [C.c_void_p, *_FPC_OUT]),
+    "sim_fp_classes_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "fp_classes_of": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_size_t, C.c_uint32, *_FPC_OUT]),
 }
 
 
@@ -286,6 +314,34 @@ def ipc_unique_id(lib: SimLib) -> bytes:
     buf = (C.c_uint8 * KB_UNIQUE_ID_BYTES)()
     lib.call("ipc_unique_id", buf, KB_UNIQUE_ID_BYTES)
     return bytes(buf)
+
+
+def _fp_classes_call(lib: SimLib, name: str, head: tuple, top: int, arrays: bool, n: int):
+    """kb_sim_fp_classes / kb_fp_classes_of with the outputs of Sim.fp_classes: a list of `top` entries and, with
+    arrays, rep and size over `n` rows."""
+    import numpy as np
+    from .classes import FpClasses
+    out, got = KbFpClasses(), C.c_size_t(0)
+    lst = (KbFpClass * max(top, 1))()
+    rep = np.zeros(n, dtype=np.uint32) if arrays else None
+    size = np.zeros(n, dtype=np.uint32) if arrays else None
+    ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32)) if a is not None else None
+    lib.call(name, *head, C.byref(out), lst if top else None, top, C.byref(got), ptr(rep), ptr(size), n if arrays else 0)
+    cls = np.array([(e.fp, e.size, e.rep) for e in lst[: got.value]], dtype=np.uint32).reshape(-1, 3)
+    return FpClasses(out.as_dict(), cls, rep, size)
+
+
+def fp_classes_of(lib: SimLib, fps, running, true_fp: int, top: int = 16, arrays: bool = True, device: int = 0):
+    """kb_fp_classes_of: the class census's kernels over host arrays of fingerprints and running flags (a test
+    surface, include/kaboodle_classes.h); an `FpClasses` with round -1.  KbError(KB_NO_DEVICE) without a GPU."""
+    import numpy as np
+    fps = np.ascontiguousarray(fps, dtype=np.uint32)
+    run = np.ascontiguousarray(np.asarray(running) != 0, dtype=np.uint8)
+    if len(fps) != len(run):
+        raise ValueError("fps and running differ in length")
+    head = (device, fps.ctypes.data_as(C.POINTER(C.c_uint32)), run.ctypes.data_as(C.POINTER(C.c_uint8)), len(fps),
+            int(true_fp) & 0xFFFFFFFF)
+    return _fp_classes_call(lib, "fp_classes_of", head, top, arrays, len(fps))
 
 
 class Sim:
@@ -536,6 +592,23 @@ class Sim:
         """Device time of the last reciprocity() in ms (kb_sim_reciprocity_device_ms; HIP library only)."""
         v = C.c_double()
         self.lib.call("sim_reciprocity_device_ms", self.h, C.byref(v))
+        return v.value
+
+    def fp_classes(self, top: int = 16, arrays: bool = True):
+        """The fingerprint-class census (include/kaboodle_classes.h): an `FpClasses` with `summary` (dict of
+        kb_fp_classes), `classes` (the first `top` <= 1024 classes in canonical order as an [n, 3] array of fp, size,
+        rep) and the uint32 arrays `rep` and `size` over all ids (None with arrays=False).  Computed on the device by
+        kb_sim_fp_classes; a library without it (the CPU oracle) answers the same call through
+        classes.fp_classes_ref, so both are compared through identical calls."""
+        if "sim_fp_classes" not in self.lib.fn:
+            from .classes import fp_classes_ref
+            return fp_classes_ref(self, top, arrays)
+        return _fp_classes_call(self.lib, "sim_fp_classes", (self.h,), top, arrays, self.capacity)
+
+    def fp_classes_device_ms(self) -> float:
+        """Device time of the last fp_classes() in ms (kb_sim_fp_classes_device_ms; HIP library only)."""
+        v = C.c_double()
+        self.lib.call("sim_fp_classes_device_ms", self.h, C.byref(v))
         return v.value
 
     def row(self, node: int):

@@ -421,6 +421,8 @@ struct kb_sim {
   uint32_t* rc_buf = nullptr;          // the reciprocity census's scratch (kb_recip.h), allocated by its first call
   uint32_t* rc_pairs = nullptr; uint64_t rc_pairs_cap = 0;   // its pair list (entries), grown on demand
   double rc_ms = 0;                    // device time of the last reciprocity census
+  void* fc_buf = nullptr; size_t fc_cap = 0;   // the class census's scratch (kb_classes.h), bytes; grown on demand
+  double fc_ms = 0;                    // device time of the last class census
   bool debug_waves = false;
   size_t lds_per_cu = 65536;
   // kb_sim_create_local: a façade over `world` in-process shards (one host thread each per step)
@@ -850,6 +852,7 @@ extern "C" int kb_sim_create_local(const kb_config* cfg, int32_t shards, kb_sim*
 
 extern "C" int kb_sim_destroy(kb_sim* s) {
   if (!s) return KB_INVALID_ARGUMENT;
+  if (s->fc_buf) { (void)hipSetDevice(s->device); (void)hipFree(s->fc_buf); s->fc_buf = nullptr; }
   if (s->sp) { destroy_one(s); return KB_OK; }
   if (!s->shards.empty()) {
     for (kb_sim* t : s->shards) destroy_one(t);
@@ -2497,3 +2500,6 @@ extern "C" int kb_sim_sparse_footprint(kb_sim* s, uint64_t* out, size_t cap) {
 
 // ---- the reciprocity census (include/kaboodle_reciprocity.h) ---------------------------------------------
 #include "kb_recip.h"
+
+// ---- the fingerprint-class census (include/kaboodle_classes.h) -------------------------------------------
+#include "kb_classes.h"

@@ -14,7 +14,9 @@ A run that ends without agreement (the cap or the budget), or any run with --rec
 census of its last state (include/kaboodle_reciprocity.h) in the result: the summary and, when it
 fits --max-pairs, the list of mutual pairs — the gaps that can never heal — in place of the eight hand-sampled
 views earlier records carry, and beside it the view census's summary, which keeps what those
-views also showed: the stale entries and the ghosts (non-running ids some view still holds).
+views also showed: the stale entries and the ghosts (non-running ids some view still holds).  Beside the two it
+records the fingerprint-class census (include/kaboodle_classes.h): its summary and the 8 largest
+classes as (fp, size, rep).
 """
 from __future__ import annotations
 
@@ -111,6 +113,11 @@ def main() -> int:
                      "rows_lacked_by": int((rc.lacked_by > 0).sum()), "device_ms": round(m.reciprocity_device_ms(), 4)}
             print(f"[converge {a.mode}] reciprocity: {json.dumps(rc.summary)}", flush=True)
             print(f"[converge {a.mode}] census: {json.dumps(recip['census'])}", flush=True)
+            # and which camps the views fall into: one second fingerprint shared by the stragglers, or each alone
+            fc = m.fp_classes(top=8, arrays=False)
+            recip["fp_classes"] = {"summary": fc.summary, "top_classes": fc.classes.tolist(),
+                                   "device_ms": round(m.fp_classes_device_ms(), 4)}
+            print(f"[converge {a.mode}] fp classes: {json.dumps(recip['fp_classes'])}", flush=True)
     out = {"workload": f"configs[2]: {n} peers, converged start, 1% loss, 0.1%/round churn, faults until round {F}",
            "failed_mode": "socket_faithful" if a.mode == "sock" else "sim_sender", "fault_end_round": F,
            "a3_order": a.lru,
