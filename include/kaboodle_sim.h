@@ -342,6 +342,44 @@ int  kb_sim_dump_curious(kb_sim* sim, uint32_t node, int32_t* out, size_t cap, s
    kbo_sparse_footprint; here 4 bytes per entry, exception and stamp packed together).  Other handles:
    KB_INVALID_OPERATION.  Test surface.                                                             */
 int  kb_sim_sparse_footprint(kb_sim* sim, uint64_t* out, size_t cap);
+/* The fingerprint checkpoints of `node` exactly as they are stored: seg[2k], seg[2k+1] = the
+   (raw, cnt) checkpoint of segment k (64 segments of W/64 ids, W = capacity rounded up to 8192), the mask of stale
+   checkpoints, the cached fingerprint's stale flag and the cached fingerprint.  Strictly read-only: nothing is
+   refolded (kb_sim_fingerprint refolds before it answers).  Dense handles, unsharded or in-process shards (answered
+   by the shard holding the row); sparse rows and kb_sim_create_rank handles: KB_INVALID_OPERATION.  Test surface. */
+int  kb_sim_dump_checkpoints(kb_sim* sim, uint32_t node, uint32_t seg[128], uint64_t* stale, uint32_t* dirty,
+                             uint32_t* fp_cached);
+/* The fingerprint kernels over rows supplied by the caller.  Test surface.
+   path:  KB_FOLD_TICK    k_fold then k_fp_rows, the tick's two launches (uniform identities only, as in the tick:
+                          a handle with non-uniform identities is left untouched)
+          KB_FOLD_FP_ALL  k_fp_all (kb_sim_fingerprints)
+          KB_FOLD_FP_ONE  k_fp_one for every listed row (kb_sim_fingerprint)
+          KB_FOLD_THREAD  the tick's thread-per-row refresh (k_tick_post's), running rows only
+   split: KB_FOLD_TICK's column splits, a power of two from 1 to 64; 0 = the handle's own.
+   rows[nrows] ascending ids; running[nrows]; bits[nrows][W/32] the member bitsets (a bit at an id >= capacity:
+   KB_INVALID_ARGUMENT); stale[nrows] the stale-checkpoint masks; segp_in[nrows][64][2] the stored checkpoints,
+   written verbatim.  The call clears `alive`, the stale masks and flags of every row, writes the listed rows (bits,
+   checkpoints, stale mask, cached fingerprint stale, alive = running), launches the path, waits, and reads the
+   listed rows back: segp_out[nrows][64][2], stale_out, dirty_out, fp_out [nrows], and *fold_bytes = the member-bit
+   bytes k_fold counted during the call.  It never runs a round.  Only on a dense handle (unsharded or in-process
+   shards) created with initial_nodes = 0 that has not stepped (else KB_INVALID_OPERATION); repeatable; afterwards
+   kb_sim_step on the handle returns KB_INVALID_OPERATION.  KB_FOLD_THREAD with a stale mask on a handle with
+   uniform identities is KB_INVALID_ARGUMENT (that path combines checkpoints and requires them fresh).          */
+enum { KB_FOLD_TICK = 0, KB_FOLD_FP_ALL = 1, KB_FOLD_FP_ONE = 2, KB_FOLD_THREAD = 3 };
+typedef struct kb_fold_probe {
+  uint32_t path, split, nrows, pad;
+  const uint32_t* rows;
+  const uint8_t*  running;
+  const uint32_t* bits;
+  const uint64_t* stale;
+  const uint32_t* segp_in;
+  uint32_t* segp_out;
+  uint64_t* stale_out;
+  uint32_t* dirty_out;
+  uint32_t* fp_out;
+  uint64_t* fold_bytes;
+} kb_fold_probe;
+int  kb_sim_debug_fold(kb_sim* sim, const kb_fold_probe* p);
 
 /* ---- pure helpers ------------------------------------------------------------------------------- */
 /* Canonical simulated address of an id: "10.100.100.<100 + id/50000>:<10000 + id%50000>".          */

@@ -124,6 +124,20 @@ _FPC_OUT = [C.POINTER(KbFpClasses), C.POINTER(KbFpClass), C.c_size_t, C.POINTER(
             C.POINTER(C.c_uint32), C.c_size_t]
 
 
+KB_FOLD_TICK, KB_FOLD_FP_ALL, KB_FOLD_FP_ONE, KB_FOLD_THREAD = 0, 1, 2, 3   # kb_fold_probe.path
+NSEG = 64                        # fingerprint checkpoints per row
+
+
+class KbFoldProbe(C.Structure):
+    """kb_fold_probe (include/kaboodle_sim.h)."""
+    _fields_ = [("path", C.c_uint32), ("split", C.c_uint32), ("nrows", C.c_uint32), ("pad", C.c_uint32),
+                ("rows", C.POINTER(C.c_uint32)), ("running", C.POINTER(C.c_uint8)), ("bits", C.POINTER(C.c_uint32)),
+                ("stale", C.POINTER(C.c_uint64)), ("segp_in", C.POINTER(C.c_uint32)),
+                ("segp_out", C.POINTER(C.c_uint32)), ("stale_out", C.POINTER(C.c_uint64)),
+                ("dirty_out", C.POINTER(C.c_uint32)), ("fp_out", C.POINTER(C.c_uint32)),
+                ("fold_bytes", C.POINTER(C.c_uint64))]
+
+
 class KbWireAddrC(C.Structure):
     _fields_ = [("ip", C.c_uint8 * 4), ("port", C.c_uint16), ("pad", C.c_uint16)]
 
@@ -256,6 +270,10 @@ _OPTIONAL = {
     "sim_kernel_breakdown": (C.c_int, [C.c_void_p, C.POINTER(KbKernelTime), C.c_size_t, C.POINTER(C.c_size_t)]),
     "sim_host_syncs": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "sim_sparse_footprint": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t]),
+    # the fingerprint checkpoints as stored and the fold probe (test surface; HIP library only)
+    "sim_dump_checkpoints": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "sim_debug_fold": (C.c_int, [C.c_void_p, C.POINTER(KbFoldProbe)]),
     # the view census (include/kaboodle_census.h; HIP library only, the oracle answers through census.census_ref)
     "sim_census": (C.c_int, [C.c_void_p, C.POINTER(KbCensus), C.POINTER(C.c_uint32), C.c_size_t,
                              C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t]),
@@ -638,6 +656,45 @@ class Sim:
         buf = (C.c_int32 * (6 * 8))()
         self.lib.call("sim_dump_curious", self.h, node, buf, len(buf), C.byref(n))
         return [tuple(buf[6 * k: 6 * k + 6]) for k in range(n.value)]
+
+    def checkpoints(self, node: int):
+        """The fingerprint checkpoints of `node` as stored, nothing refolded (kb_sim_dump_checkpoints): (seg, stale,
+        dirty, fp_cached) with seg a uint32 [64, 2] array of (raw, cnt), stale the mask of stale checkpoints, dirty
+        the cached fingerprint's stale flag."""
+        import numpy as np
+        seg = np.zeros((NSEG, 2), dtype=np.uint32)
+        stale, dirty, fp = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        self.lib.call("sim_dump_checkpoints", self.h, node, seg.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(stale),
+                      C.byref(dirty), C.byref(fp))
+        return seg, stale.value, dirty.value, fp.value
+
+    def fold_probe(self, path: int, rows, running, bits, stale, segp_in, split: int = 0):
+        """kb_sim_debug_fold: the fingerprint kernels of `path` (KB_FOLD_*) over the caller's rows.  rows: ascending
+        ids; running: a flag per row; bits: uint32 [nrows, W/32] member bitsets (W = capacity rounded up to 8192);
+        stale: a uint64 mask per row; segp_in: uint32 [nrows, 64, 2] checkpoints, stored verbatim.  Returns (segp_out
+        [nrows, 64, 2], stale_out, dirty_out, fp_out, fold_bytes).  The handle never steps afterwards."""
+        import numpy as np
+        n = len(rows)
+        W = (self.capacity + 8191) // 8192 * 8192
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        run = np.ascontiguousarray(np.asarray(running) != 0, dtype=np.uint8)
+        bits = np.ascontiguousarray(bits, dtype=np.uint32)
+        st = np.ascontiguousarray(stale, dtype=np.uint64)
+        sin = np.ascontiguousarray(segp_in, dtype=np.uint32)
+        if run.shape != (n,) or st.shape != (n,) or bits.shape != (n, W // 32) or sin.shape != (n, NSEG, 2):
+            raise ValueError("fold_probe: array shapes do not match the rows")
+        sout = np.zeros((n, NSEG, 2), dtype=np.uint32)
+        stout = np.zeros(n, dtype=np.uint64)
+        dout, fout = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        fb = C.c_uint64()
+        u32, u64 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+        p = KbFoldProbe(path=path, split=split, nrows=n, rows=rows.ctypes.data_as(u32),
+                        running=run.ctypes.data_as(C.POINTER(C.c_uint8)), bits=bits.ctypes.data_as(u32),
+                        stale=st.ctypes.data_as(u64), segp_in=sin.ctypes.data_as(u32), segp_out=sout.ctypes.data_as(u32),
+                        stale_out=stout.ctypes.data_as(u64), dirty_out=dout.ctypes.data_as(u32),
+                        fp_out=fout.ctypes.data_as(u32), fold_bytes=C.pointer(fb))
+        self.lib.call("sim_debug_fold", self.h, C.byref(p))
+        return sout, stout, dout, fout, fb.value
 
     def format_addr(self, node: int) -> str:
         buf = C.create_string_buffer(32)

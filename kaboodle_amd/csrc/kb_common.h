@@ -383,6 +383,20 @@ __device__ inline uint32_t thread_fp(const Dev& d, uint32_t i) {
   }
   return finish_fp(d, raw, cnt);
 }
+// the cached fingerprint of row i brought up to date by one thread (k_tick_post; the fold probe's thread path):
+// non-uniform identities refold their stale checkpoints here, serially; uniform rows reach this with fresh ones
+__device__ __attribute__((always_inline)) inline void thread_refresh_fp(const Dev& d, uint32_t i) {
+  if (d.dirty[i]) {
+    if (!d.uniform && d.sdirty[i]) {            // non-uniform identities: refold stale checkpoints here
+      unsigned long long sd = d.sdirty[i];
+      while (sd) { const int k = __ffsll((long long)sd) - 1; sd &= sd - 1;
+                   d.segp[(size_t)i * NSEG + k] = fold_segment(d, nullptr, i, k); }
+      d.sdirty[i] = 0;
+    }
+    d.fp[i] = thread_fp(d, i);
+    d.dirty[i] = 0;
+  }
+}
 
 // position of the rem-th (0-based) set bit of x: a five-step popcount descent, no loop
 __device__ inline uint32_t select_in_word(uint32_t x, uint32_t rem) {

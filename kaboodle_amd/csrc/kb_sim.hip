@@ -353,6 +353,7 @@ struct kb_sim {
   bool in_group;                       // a shard of a kb_sim_create_local group
   std::vector<void*> allocs;           // device memory owned by this handle
   int32_t round;
+  bool probed = false;                 // kb_sim_debug_fold wrote rows of its own: the handle steps no more
   std::vector<uint8_t> h_ident, h_idlen;
   std::vector<uint8_t> h_pend; std::vector<int16_t> h_pendlen;   // identity set on a stopped instance that ran:
                                                                  // its next address takes it (-1: none)
@@ -1653,6 +1654,7 @@ static int group_step(kb_sim* g, uint32_t rounds) {
 extern "C" int kb_sim_step(kb_sim* s, uint32_t rounds) {
   if (s && s->sp) return sp_step(s->sp, rounds);
   if (!s) return KB_INVALID_ARGUMENT;
+  if (s->probed) { seterr("the handle ran the fold probe (kb_sim_debug_fold): it cannot step"); return KB_INVALID_OPERATION; }
   if (is_group(s)) return group_step(s, rounds);
   (void)hipSetDevice(s->device);
   for (uint32_t k = 0; k < rounds; ++k) {
@@ -2493,6 +2495,122 @@ extern "C" int kb_sim_sparse_footprint(kb_sim* s, uint64_t* out, size_t cap) {
   }
   if (!s->sp) { seterr("not a KB_VARIANT_SPARSE_ROWS handle"); return KB_INVALID_OPERATION; }
   return sp_footprint(s->sp, out, cap);
+}
+
+// ---- the fingerprint checkpoints as stored, and the fold probe (test surface) -------------
+static bool fold_surface_ok(kb_sim* s) {             // dense, and no rank of a kb_sim_create_rank mesh
+  if (!s || s->sp || sp_grp(s)) { seterr("dense handles only"); return false; }
+  if (!is_group(s) && s->xf && !s->in_group) { seterr("not on a kb_sim_create_rank handle"); return false; }
+  return true;
+}
+extern "C" int kb_sim_dump_checkpoints(kb_sim* s, uint32_t node, uint32_t* seg, uint64_t* stale, uint32_t* dirty,
+                                       uint32_t* fp_cached) {
+  if (!s) return KB_INVALID_ARGUMENT;
+  if (!fold_surface_ok(s)) return KB_INVALID_OPERATION;
+  if (chk(s, node) || !seg || !stale || !dirty || !fp_cached) return KB_INVALID_ARGUMENT;
+  GROUP_OWNER(node, [&](kb_sim* t) { return kb_sim_dump_checkpoints(t, node, seg, stale, dirty, fp_cached); });
+  if (chk_row(s, node)) return KB_INVALID_ARGUMENT;
+  (void)hipSetDevice(s->device);
+  uint8_t dy = 0;
+  HIPCHK(hipMemcpy(seg, s->d.segp + (size_t)node * NSEG, 8ull * NSEG, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(stale, s->d.sdirty + node, 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&dy, s->d.dirty + node, 1, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(fp_cached, s->d.fp + node, 4, hipMemcpyDeviceToHost));
+  *dirty = dy;
+  return KB_OK;
+}
+
+// the tick's thread-per-row fingerprint refresh alone (k_tick_post's), for the probe
+__global__ void k_probe_thread_fp(Dev d) {
+  const uint32_t i = d.lo + blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < d.hi && d.alive[i]) thread_refresh_fp(d, i);
+}
+// one shard's part of a probe: the listed rows it holds
+static int fold_probe_shard(kb_sim* s, const kb_fold_probe* p, uint64_t* fold_bytes) {
+  (void)hipSetDevice(s->device);
+  const Dev& d = s->d;
+  const uint32_t R = s->R, NWR = d.NWR;
+  HIPCHK(hipStreamSynchronize(s->st));
+  const uint64_t b0 = stat_counter(s, S_FOLDB);
+  HIPCHK(hipMemset(d.alive, 0, s->C));
+  HIPCHK(hipMemset(L(s, d.dirty), 0, R));
+  HIPCHK(hipMemset(L(s, d.sdirty), 0, 8ull * R));
+  for (uint32_t q = 0; q < p->nrows; ++q) {
+    const uint32_t i = p->rows[q];
+    const uint8_t run = p->running[q] ? 1 : 0, one = 1;
+    HIPCHK(hipMemcpy(d.alive + i, &run, 1, hipMemcpyHostToDevice));          // per id: replicated on every shard
+    if (i < s->lo || i >= s->hi) continue;
+    HIPCHK(hipMemcpy(d.bits + (size_t)i * NWR, p->bits + (size_t)q * NWR, 4ull * NWR, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d.segp + (size_t)i * NSEG, p->segp_in + (size_t)q * NSEG * 2, 8ull * NSEG, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d.sdirty + i, p->stale + q, 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d.dirty + i, &one, 1, hipMemcpyHostToDevice));
+  }
+  HIPCHK(hipDeviceSynchronize());
+  const uint32_t tb = 256;
+  if (p->path == KB_FOLD_TICK) {                     // the two launches of step_round's tick, with the split asked for
+    const uint32_t S = p->split ? p->split : s->S;
+    if (d.uniform) k_fold<<<dim3(((R + 63) / 64 + 3) / 4 * S), dim3(256), 0, s->st>>>(d, FoldArgs{S});
+    if (d.uniform) k_fp_rows<<<dim3((FP_LANES * R + tb - 1) / tb), dim3(tb), 0, s->st>>>(d);
+  } else if (p->path == KB_FOLD_FP_ALL) {
+    k_fp_all<<<(R + 3) / 4, 256, 0, s->st>>>(d);
+  } else if (p->path == KB_FOLD_FP_ONE) {
+    for (uint32_t q = 0; q < p->nrows; ++q)
+      if (p->rows[q] >= s->lo && p->rows[q] < s->hi) k_fp_one<<<1, 64, 0, s->st>>>(d, p->rows[q]);
+  } else {
+    k_probe_thread_fp<<<(R + tb - 1) / tb, tb, 0, s->st>>>(d);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(s->st));
+  for (uint32_t q = 0; q < p->nrows; ++q) {
+    const uint32_t i = p->rows[q];
+    if (i < s->lo || i >= s->hi) continue;
+    uint8_t dy = 0;
+    HIPCHK(hipMemcpy(p->segp_out + (size_t)q * NSEG * 2, d.segp + (size_t)i * NSEG, 8ull * NSEG, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(p->stale_out + q, d.sdirty + i, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&dy, d.dirty + i, 1, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(p->fp_out + q, d.fp + i, 4, hipMemcpyDeviceToHost));
+    p->dirty_out[q] = dy;
+  }
+  *fold_bytes += stat_counter(s, S_FOLDB) - b0;
+  return KB_OK;
+}
+extern "C" int kb_sim_debug_fold(kb_sim* s, const kb_fold_probe* p) {
+  if (!s || !p) return KB_INVALID_ARGUMENT;
+  if (!fold_surface_ok(s)) return KB_INVALID_OPERATION;
+  kb_sim* h = is_group(s) ? s->shards[0] : s;
+  if (s->cfg.initial_nodes != 0 || h->round != 0) {
+    seterr("the fold probe needs a handle created with initial_nodes = 0 that has not stepped"); return KB_INVALID_OPERATION;
+  }
+  if (p->path > KB_FOLD_THREAD || p->split > 64 || (p->split & (p->split - 1)) || !p->nrows || !p->rows || !p->running ||
+      !p->bits || !p->stale || !p->segp_in || !p->segp_out || !p->stale_out || !p->dirty_out || !p->fp_out || !p->fold_bytes) {
+    seterr("fold probe: path, split (a power of two up to 64, or 0) or a null array"); return KB_INVALID_ARGUMENT;
+  }
+  const uint32_t C = s->C, NWR = h->d.NWR;
+  for (uint32_t q = 0; q < p->nrows; ++q) {
+    if (p->rows[q] >= C || (q && p->rows[q] <= p->rows[q - 1])) { seterr("fold probe: rows are ascending ids below the capacity"); return KB_INVALID_ARGUMENT; }
+    if (p->path == KB_FOLD_THREAD && h->d.uniform && p->stale[q]) { seterr("fold probe: the thread path needs fresh checkpoints on uniform identities"); return KB_INVALID_ARGUMENT; }
+    const uint32_t* b = p->bits + (size_t)q * NWR;
+    for (uint32_t w = C / 32; w < NWR; ++w)
+      if (w * 32 >= C ? b[w] != 0 : (b[w] >> (C & 31)) != 0) { seterr("fold probe: a member bit at an id >= capacity"); return KB_INVALID_ARGUMENT; }
+    // the kernels index Z^cnt tables of capacity + 2 entries by the counts they combine: what the fresh checkpoints
+    // claim plus what the stale segments hold must stay a member count of this capacity
+    uint64_t total = 0;
+    const uint32_t wps = NWR / NSEG;                 // bitset words per segment
+    for (uint32_t k = 0; k < (uint32_t)NSEG && h->d.uniform; ++k) {
+      if (!((p->stale[q] >> k) & 1ull)) { total += p->segp_in[((size_t)q * NSEG + k) * 2 + 1]; continue; }
+      for (uint32_t w = k * wps; w < (k + 1) * wps; ++w) total += (uint32_t)__builtin_popcount(b[w]);
+    }
+    if (total > C) { seterr("fold probe: the checkpoints' member counts exceed the capacity"); return KB_INVALID_ARGUMENT; }
+  }
+  s->probed = true;                                  // no round after a probe: its rows are no simulator state
+  *p->fold_bytes = 0;
+  std::vector<kb_sim*> one{s};
+  for (kb_sim* t : is_group(s) ? s->shards : one) {
+    t->probed = true;
+    const int rc = fold_probe_shard(t, p, p->fold_bytes);
+    if (rc) return rc;
+  }
+  return KB_OK;
 }
 
 // ---- the view census (include/kaboodle_census.h) ----------------------------------------------------------

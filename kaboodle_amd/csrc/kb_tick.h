@@ -311,16 +311,7 @@ __global__ void k_tick_post(Dev d, RowOut ro, OutBuf ob, int32_t r) {
     }
     d.paq_n[i] = 0;
     ob.cnt[i] = oseq;
-    if (d.dirty[i]) {
-      if (!d.uniform && d.sdirty[i]) {            // non-uniform identities: refold stale checkpoints here
-        unsigned long long sd = d.sdirty[i];
-        while (sd) { const int k = __ffsll((long long)sd) - 1; sd &= sd - 1;
-                     d.segp[(size_t)i * NSEG + k] = fold_segment(d, nullptr, i, k); }
-        d.sdirty[i] = 0;
-      }
-      d.fp[i] = thread_fp(d, i);
-      d.dirty[i] = 0;
-    }
+    thread_refresh_fp(d, i);
     agree = d.fp[i] == d.truefp[0];
   }
   const unsigned long long t = block_sum(agree);
