@@ -361,7 +361,7 @@ extern "C" int kb_sim_fp_classes(kb_sim* s, kb_fp_classes* out, kb_fp_class* lis
   if (!s) return KB_INVALID_ARGUMENT;
   { const int rc = fc_check(out, list, cap_list, rep, size, cap_rows, s->C, "kb_sim_fp_classes"); if (rc) return rc; }
   const bool grp = is_group(s);
-  if (!grp && (s->sp ? s->sp->xf : s->xf)) {
+  if (kind_of(s).rank) {
     seterr("kb_sim_fp_classes: a rank handle holds its own rows only and a class spans ranks (use kb_sim_create or kb_sim_create_local)");
     return KB_INVALID_OPERATION;
   }

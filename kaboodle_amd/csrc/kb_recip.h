@@ -207,10 +207,10 @@ __global__ __launch_bounds__(RC_THREADS) void k_rc_pairs(RcArgs a) {
 extern "C" int kb_sim_reciprocity(kb_sim* s, kb_reciprocity* out, uint32_t* mutual, uint32_t* lacks, uint32_t* lacked_by,
                                   size_t cap_rows, uint32_t* pairs, size_t cap_pairs) {
   if (!s || !out) return KB_INVALID_ARGUMENT;
-  if (s->sp || (is_group(s) && s->shards[0]->sp)) {
+  if (kind_of(s).sparse) {
     seterr("kb_sim_reciprocity: sparse rows need an O(entries) algorithm of their own (not built yet)"); return KB_INVALID_OPERATION;
   }
-  if (!is_group(s) && s->xf) {
+  if (kind_of(s).rank) {
     seterr("kb_sim_reciprocity: a rank handle holds its own rows only; the census needs every rank's (use kb_sim_create or kb_sim_create_local)");
     return KB_INVALID_OPERATION;
   }

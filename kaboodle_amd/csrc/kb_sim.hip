@@ -776,6 +776,40 @@ constexpr uint32_t KB_FOLD_WAVES = 16384;                            // fold wav
   return KB_OK;
 }
 
+// ---- the router: four kinds of handle behind one kb_sim* (DESIGN.md "Host control plane") ------------------
+// A leaf is a dense shard or a wrapper of a sparse engine (sp); a kb_sim_create_local group holds leaves of one sort.
+static bool is_group(const kb_sim* s) { return !s->shards.empty(); }
+struct Kind { bool sparse, group, rank; };           // rank: one rank of a kb_sim_create_rank mesh (its own rows only)
+static Kind kind_of(const kb_sim* s) {
+  const kb_sim* f = is_group(s) ? s->shards[0] : s;
+  const bool leaf_xf = f->sp ? f->sp->xf != nullptr : f->xf != nullptr;
+  return Kind{f->sp != nullptr, is_group(s), !is_group(s) && leaf_xf && !s->in_group};
+}
+static kb_sim* owner(kb_sim* g, uint32_t node) {     // the shard holding node's row
+  for (kb_sim* t : g->shards) if (node >= t->lo && node < t->hi) return t;
+  return nullptr;
+}
+// f on a leaf's engine: a generic callable, f(kb_sim*) for a dense shard and f(SpSim*) for the sparse rows
+template <class F> static int visit(kb_sim* leaf, F&& f) { return leaf->sp ? f(leaf->sp) : f(leaf); }
+// R_ALL: every shard in rank order, the first error wins (mesh-changing calls; with a callable that accumulates,
+// the fold of the merging calls); R_OWNER: the shard holding node's row; R_FIRST: the first shard (replicated facts).
+// A leaf handle answers every policy itself.  The shard's device is current while f runs.
+enum Route { R_ALL, R_OWNER, R_FIRST };
+template <class F> static int route(kb_sim* s, Route how, uint32_t node, F&& f) {
+  if (!is_group(s)) return visit(s, f);
+  if (how != R_ALL) {
+    kb_sim* t = how == R_OWNER ? owner(s, node) : s->shards[0];
+    (void)hipSetDevice(t->device);
+    return visit(t, f);
+  }
+  for (kb_sim* t : s->shards) {
+    (void)hipSetDevice(t->device);
+    const int rc = visit(t, f);
+    if (rc) return rc;
+  }
+  return KB_OK;
+}
+
 static void destroy_one(kb_sim* s) {                 // a dense shard, or a sparse handle (its engine owns the exchange)
   if (s->sp) { sp_destroy(s->sp); delete s; return; }
   destroy_shard(s);
@@ -854,23 +888,17 @@ extern "C" int kb_sim_create_local(const kb_config* cfg, int32_t shards, kb_sim*
 extern "C" int kb_sim_destroy(kb_sim* s) {
   if (!s) return KB_INVALID_ARGUMENT;
   if (s->fc_buf) { (void)hipSetDevice(s->device); (void)hipFree(s->fc_buf); s->fc_buf = nullptr; }
-  if (s->sp) { destroy_one(s); return KB_OK; }
-  if (!s->shards.empty()) {
-    for (kb_sim* t : s->shards) destroy_one(t);
-    delete s->hub;
-    delete s;
-    return KB_OK;
-  }
-  destroy_shard(s);
+  if (!is_group(s)) { destroy_one(s); return KB_OK; }
+  for (kb_sim* t : s->shards) destroy_one(t);
+  delete s->hub;
+  delete s;
   return KB_OK;
 }
 
 extern "C" int kb_sim_shard_info(kb_sim* s, int32_t* rank, int32_t* world, uint32_t* lo, uint32_t* hi) {
-  if (s && s->sp && rank && world && lo && hi) { *rank = s->sp->rank; *world = s->sp->world; *lo = s->sp->lo; *hi = s->sp->hi; return KB_OK; }
   if (!s || !rank || !world || !lo || !hi) return KB_INVALID_ARGUMENT;
-  if (!s->shards.empty()) { *rank = 0; *world = s->world; *lo = 0; *hi = s->C; return KB_OK; }
-  *rank = s->rank; *world = s->world; *lo = s->lo; *hi = s->hi;
-  return KB_OK;
+  if (is_group(s)) { *rank = 0; *world = s->world; *lo = 0; *hi = s->C; return KB_OK; }
+  return visit(s, [&](auto* e) { *rank = e->rank; *world = e->world; *lo = e->lo; *hi = e->hi; return KB_OK; });
 }
 
 // Host side of the pinned hand-offs: spin on the mapped sequence word (a stream synchronisation would
@@ -1605,26 +1633,6 @@ static int step_round(kb_sim* s) {
   return err_status(err);                            // shards: the flag of any rank
 }
 
-static bool is_group(const kb_sim* s) { return !s->shards.empty(); }
-static kb_sim* owner(kb_sim* g, uint32_t node) {                 // the shard holding node's row
-  for (kb_sim* t : g->shards) if (node >= t->lo && node < t->hi) return t;
-  return nullptr;
-}
-// a kb_sim_create_local group of sparse-row shards: mesh-changing calls go to every shard, row inspection to the
-// shard holding the row, replicated facts to the first shard
-static bool sp_grp(const kb_sim* s) { return s && !s->shards.empty() && s->shards[0]->sp; }
-#define SPG_ALL(call)                                                     \
-  if (sp_grp(s)) {                                                        \
-    for (kb_sim* t_ : s->shards) { const int rc_ = call(t_); if (rc_) return rc_; } \
-    return KB_OK;                                                         \
-  }
-#define SPG_OWNER(node, call)                                             \
-  if (sp_grp(s)) {                                                        \
-    if (node >= s->C) return KB_INVALID_ARGUMENT;                         \
-    return call(owner(s, node));                                          \
-  }
-#define SPG_FIRST(call) if (sp_grp(s)) return call(s->shards[0]);
-
 // every shard of a group steps in its own thread; a failing shard aborts the others' rendezvous
 static int group_step(kb_sim* g, uint32_t rounds) {
   const size_t W = g->shards.size();
@@ -1652,10 +1660,10 @@ static int group_step(kb_sim* g, uint32_t rounds) {
 }
 
 extern "C" int kb_sim_step(kb_sim* s, uint32_t rounds) {
-  if (s && s->sp) return sp_step(s->sp, rounds);
   if (!s) return KB_INVALID_ARGUMENT;
   if (s->probed) { seterr("the handle ran the fold probe (kb_sim_debug_fold): it cannot step"); return KB_INVALID_OPERATION; }
   if (is_group(s)) return group_step(s, rounds);
+  if (s->sp) return sp_step(s->sp, rounds);
   (void)hipSetDevice(s->device);
   for (uint32_t k = 0; k < rounds; ++k) {
     int rc = step_round(s);
@@ -1666,15 +1674,10 @@ extern "C" int kb_sim_step(kb_sim* s, uint32_t rounds) {
 }
 
 // ---------------------------------------------------------------------------------- API surface
-// Sharded handles: calls that change the mesh (start/stop/set_identity/ping_addrs) are made on every
-// shard alike; row inspection is answered by the shard holding the row (KB_INVALID_ARGUMENT on the
-// others); kb_sim_stats is a collective over the ranks of kb_sim_create_rank.
+// Every entry point checks its arguments once and hands the call to route() (above); what the call does on one
+// engine is a kb_ctl.h template, or an eng_* overload where the engines really differ.  Which calls go to every
+// shard, to the owner of a row or to the first shard, and which merge: DESIGN.md "Host control plane".
 static int chk(kb_sim* s, uint32_t node) { return (!s || node >= s->C) ? KB_INVALID_ARGUMENT : KB_OK; }
-static int chk_row(kb_sim* s, uint32_t node) {
-  if (chk(s, node)) return KB_INVALID_ARGUMENT;
-  if (node < s->lo || node >= s->hi) { seterr("the node's row is held by another shard"); return KB_INVALID_ARGUMENT; }
-  return KB_OK;
-}
 static int read_row(kb_sim* s, uint32_t node, std::vector<uint8_t>& rw) {   // canonical bytes (0 = not a member)
   std::vector<uint32_t> bw(s->d.NWR);
   rw.resize(s->C);
@@ -1684,294 +1687,116 @@ static int read_row(kb_sim* s, uint32_t node, std::vector<uint8_t>& rw) {   // c
   return KB_OK;
 }
 
-#define GROUP_ALL(call)                                                   \
-  if (is_group(s)) {                                                      \
-    for (kb_sim* t_ : s->shards) { const int rc_ = call(t_); if (rc_) return rc_; } \
-    return KB_OK;                                                         \
-  }
-#define GROUP_OWNER(node, call)                                           \
-  if (is_group(s)) {                                                      \
-    if (chk(s, node)) return KB_INVALID_ARGUMENT;                         \
-    return call(owner(s, node));                                          \
-  }
+#include "kb_ctl.h"
 
-// running as the API sees it: the last lifecycle call queued for the node since the last step (they take
-// effect at the next round start), else its current state; a queued restart moves the instance away
-static int api_running(kb_sim* s, uint32_t node, int* run) {
-  for (size_t k = s->events.size(); k-- > 0;) {
-    if (s->events[k].node == node) { *run = s->events[k].kind != EV_STOP; return KB_OK; }
-    if (s->events[k].kind == EV_RESTART && s->events[k].src == node) { *run = 0; return KB_OK; }
-  }
-  uint8_t a = 0;
-  HIPCHK(hipMemcpy(&a, s->d.alive + node, 1, hipMemcpyDeviceToHost));
-  *run = a;
-  return KB_OK;
-}
-// the address has been bound by an instance: it ran (start_round, replicated), or a start of it is queued
-static int ever_bound(kb_sim* s, uint32_t node, int* ever) {
-  for (const Event& e : s->events) if (e.node == node && e.kind != EV_STOP) { *ever = 1; return KB_OK; }
-  int32_t sr = 0;
-  HIPCHK(hipMemcpy(&sr, s->d.start_round + node, 4, hipMemcpyDeviceToHost));
-  *ever = sr != NONE_ROUND;
-  return KB_OK;
-}
-extern "C" int kb_sim_start_node(kb_sim* s, uint32_t node) {
-  if (s && s->sp) return chk(s, node) ? KB_INVALID_ARGUMENT : sp_start_node(s->sp, node);
-  SPG_ALL([&](kb_sim* t) { return kb_sim_start_node(t, node); });
-  if (chk(s, node)) return KB_INVALID_ARGUMENT;
-  kb_sim* h = is_group(s) ? s->shards[0] : s;        // lifecycle facts are replicated on every shard
-  int run = 0, ever = 0;
-  { int rc = api_running(h, node, &run); if (!rc) rc = ever_bound(h, node, &ever); if (rc) return rc; }
-  if (!run && ever) { seterr("a stopped instance restarts at a fresh address (kb_sim_restart_node)"); return KB_INVALID_OPERATION; }
-  GROUP_ALL([&](kb_sim* t) { t->events.push_back(Event{node, EV_START, node, 0}); return KB_OK; });
-  s->events.push_back(Event{node, EV_START, node, 0});
-  return KB_OK;
-}
-extern "C" int kb_sim_stop_node(kb_sim* s, uint32_t node) {
-  if (s && s->sp) return chk(s, node) ? KB_INVALID_ARGUMENT : sp_stop_node(s->sp, node);
-  SPG_ALL([&](kb_sim* t) { return kb_sim_stop_node(t, node); });
-  if (chk(s, node)) return KB_INVALID_ARGUMENT;
-  GROUP_ALL([&](kb_sim* t) { return kb_sim_stop_node(t, node); });
-  s->events.push_back(Event{node, EV_STOP, node, 0});
-  return KB_OK;
-}
-// Kaboodle::start of the instance at `node` (include/kaboodle_sim.h): a stopped instance that ran comes
-// back at the next fresh id, allocated now (the churn reserve's counter, replicated on every shard)
-static int restart_apply(kb_sim* s, uint32_t node, uint32_t to) {
-  const int pl = s->h_pendlen[node];
-  const uint8_t* src = pl >= 0 ? &s->h_pend[(size_t)node * MAXID] : &s->h_ident[(size_t)node * MAXID];
-  const uint32_t len = pl >= 0 ? (uint32_t)pl : s->h_idlen[node];
-  memmove(&s->h_ident[(size_t)to * MAXID], src, len);
-  s->h_idlen[to] = (uint8_t)len;
-  s->h_pendlen[node] = -1; s->h_pendlen[to] = -1;
-  const int rc = upload_segments(s);
-  if (rc) return rc;
-  s->buf_gen++;                                    // a captured receive window holds the old Dev (uniform)
-  const uint32_t nf = to + 1;
-  HIPCHK(hipMemcpy(s->d.ctr + C_NEXTFREE, &nf, 4, hipMemcpyHostToDevice));
-  s->events.push_back(Event{to, EV_RESTART, node, 0});
-  s->h_moved[node] = 1;
-  return KB_OK;
-}
-extern "C" int kb_sim_restart_node(kb_sim* s, uint32_t node, uint32_t* new_node) {
-  if (s && s->sp) return (chk(s, node) || !new_node) ? KB_INVALID_ARGUMENT : sp_restart_node(s->sp, node, new_node);
-  if (sp_grp(s)) {                                   // every shard allocates the same fresh id (replicated counter)
-    if (chk(s, node) || !new_node) return KB_INVALID_ARGUMENT;
-    for (size_t k = 0; k < s->shards.size(); ++k) {
-      uint32_t to = 0;
-      const int rc = kb_sim_restart_node(s->shards[k], node, &to);
-      if (rc) return rc;
-      if (k && to != *new_node) { seterr("shards allocated different fresh ids"); return KB_IO_ERROR; }
-      *new_node = to;
-    }
-    return KB_OK;
-  }
-  if (chk(s, node) || !new_node) return KB_INVALID_ARGUMENT;
-  kb_sim* h = is_group(s) ? s->shards[0] : s;
-  if (h->h_moved[node]) { seterr("the instance bound here restarted at a fresh address"); return KB_INVALID_OPERATION; }
-  int run = 0, ever = 0;
-  { int rc = api_running(h, node, &run); if (!rc) rc = ever_bound(h, node, &ever); if (rc) return rc; }
-  if (run) { *new_node = node; return KB_OK; }
-  if (!ever) {
-    *new_node = node;
-    GROUP_ALL([&](kb_sim* t) { t->events.push_back(Event{node, EV_START, node, 0}); return KB_OK; });
-    s->events.push_back(Event{node, EV_START, node, 0});
-    return KB_OK;
-  }
-  uint32_t nf = 0;
-  HIPCHK(hipMemcpy(&nf, h->d.ctr + C_NEXTFREE, 4, hipMemcpyDeviceToHost));
-  for (; nf < s->C; ++nf) {                          // the next fresh id: never bound, no identity set
-    int ev = 0;
-    const int rc = ever_bound(h, nf, &ev);
-    if (rc) return rc;
-    if (!ev && !h->h_idset[nf]) break;
-  }
-  if (nf >= s->C) { seterr("no fresh address left for the restart (capacity)"); return KB_CAPACITY; }
-  *new_node = nf;
-  GROUP_ALL([&](kb_sim* t) { (void)hipSetDevice(t->device); return restart_apply(t, node, nf); });
-  return restart_apply(s, node, nf);
-}
-extern "C" int kb_sim_is_running(kb_sim* s, uint32_t node, int* running) {
-  if (s && s->sp) return (chk(s, node) || !running) ? KB_INVALID_ARGUMENT : sp_is_running(s->sp, node, running);
-  SPG_FIRST([&](kb_sim* t) { return kb_sim_is_running(t, node, running); });
-  if (chk(s, node) || !running) return KB_INVALID_ARGUMENT;
-  if (is_group(s)) return kb_sim_is_running(s->shards[0], node, running);
-  uint8_t a = 0;
-  HIPCHK(hipMemcpy(&a, s->d.alive + node, 1, hipMemcpyDeviceToHost));
-  *running = a;
-  return KB_OK;
-}
-extern "C" int kb_sim_ping_addrs(kb_sim* s, uint32_t node, const uint32_t* peers, size_t n) {
-  if (s && s->sp) return (chk(s, node) || (n && !peers)) ? KB_INVALID_ARGUMENT : sp_ping_addrs(s->sp, node, peers, n);
-  SPG_ALL([&](kb_sim* t) { return kb_sim_ping_addrs(t, node, peers, n); });
-  if (chk(s, node) || (n && !peers)) return KB_INVALID_ARGUMENT;
-  GROUP_OWNER(node, [&](kb_sim* t) { return kb_sim_ping_addrs(t, node, peers, n); });
-  for (size_t k = 0; k < n; ++k) if (peers[k] >= s->C) return KB_INVALID_ARGUMENT;
-  uint8_t a = 0;
-  HIPCHK(hipMemcpy(&a, s->d.alive + node, 1, hipMemcpyDeviceToHost));
-  if (!a) { seterr("Cannot ping while we are not started"); return KB_INVALID_OPERATION; }
-  if (node < s->lo || node >= s->hi) return KB_OK;              // queued by the shard holding the row
-  uint32_t qn = 0;
-  HIPCHK(hipMemcpy(&qn, s->d.paq_n + node, 4, hipMemcpyDeviceToHost));
-  std::vector<uint32_t> q(PAQ), bw(s->d.NWR);
-  HIPCHK(hipMemcpy(q.data(), s->d.paq + (size_t)node * PAQ, 4 * PAQ, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(bw.data(), s->d.bits + (size_t)node * s->d.NWR, 4ull * s->d.NWR, hipMemcpyDeviceToHost));
-  for (size_t k = 0; k < n; ++k) {
-    if ((bw[peers[k] >> 5] >> (peers[k] & 31)) & 1u) continue;      // already known: skipped (:277-282)
-    if (qn == PAQ) { seterr("ping_addrs queue full"); return KB_CAPACITY; }
-    q[qn++] = peers[k];
-  }
-  HIPCHK(hipMemcpy(s->d.paq + (size_t)node * PAQ, q.data(), 4 * PAQ, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(s->d.paq_n + node, &qn, 4, hipMemcpyHostToDevice));
-  return KB_OK;
-}
-extern "C" int kb_sim_set_identity(kb_sim* s, uint32_t node, const uint8_t* identity, size_t len) {
-  if (s && s->sp) return (chk(s, node) || len > MAXID || (len && !identity)) ? KB_INVALID_ARGUMENT : sp_set_identity(s->sp, node, identity, len);
-  SPG_ALL([&](kb_sim* t) { return kb_sim_set_identity(t, node, identity, len); });
-  if (chk(s, node) || len > MAXID || (len && !identity)) return KB_INVALID_ARGUMENT;
-  GROUP_ALL([&](kb_sim* t) { return kb_sim_set_identity(t, node, identity, len); });
-  if (s->h_moved[node]) { seterr("the instance bound here restarted at a fresh address"); return KB_INVALID_OPERATION; }
-  int run = 0, ever = 0;
-  { int rc = api_running(s, node, &run); if (!rc) rc = ever_bound(s, node, &ever); if (rc) return rc; }
-  if (run) { seterr("Cannot change identity while the mesh is running; call .stop first"); return KB_INVALID_OPERATION; }
-  if (len != s->cfg.id_len && s->C > 200) { seterr("non-uniform identity length needs capacity <= 200"); return KB_INVALID_ARGUMENT; }
-  if (ever) {                                      // views keep what the address announced; the instance's
-    memcpy(&s->h_pend[(size_t)node * MAXID], identity, len);   // next address takes the new bytes
-    s->h_pendlen[node] = (int16_t)len;
-    return KB_OK;
-  }
-  memcpy(&s->h_ident[(size_t)node * MAXID], identity, len);
-  s->h_idlen[node] = (uint8_t)len;
-  s->h_idset[node] = 1;                            // no longer a fresh id for churn joins and restarts
-  { const uint8_t one = 1; HIPCHK(hipMemcpy(s->d.idset + node, &one, 1, hipMemcpyHostToDevice)); }
-  int rc = upload_segments(s);
-  if (rc) return rc;
-  s->buf_gen++;                                    // a captured receive window holds the old Dev (uniform, L)
+// ---- the dense engine's hooks (kb_ctl.h; upload_segments and read_row above) -------------------------------
+static int mark_all_dirty(kb_sim* s) {
   k_mark_all_dirty<<<(s->R + 255) / 256, 256, 0, s->st>>>(s->d);
   HIPCHK(hipStreamSynchronize(s->st));
   return KB_OK;
 }
-extern "C" int kb_sim_identity(kb_sim* s, uint32_t node, uint8_t* buf, size_t cap, size_t* len) {
-  if (s && s->sp) return (chk(s, node) || !len) ? KB_INVALID_ARGUMENT : sp_identity(s->sp, node, buf, cap, len);
-  SPG_FIRST([&](kb_sim* t) { return kb_sim_identity(t, node, buf, cap, len); });
-  if (chk(s, node) || !len) return KB_INVALID_ARGUMENT;
-  if (is_group(s)) return kb_sim_identity(s->shards[0], node, buf, cap, len);   // replicated per id
-  *len = s->h_idlen[node];
-  if (!buf) return KB_OK;
-  if (cap < *len) return KB_CAPACITY;
-  memcpy(buf, &s->h_ident[(size_t)node * MAXID], *len);
+static void window_stale(kb_sim* s) { s->buf_gen++; }   // a captured receive window holds the old Dev and buffers
+static int export_alloc(kb_sim* s) {
+  s->d.xrec_cap = XREC_MIN; s->d.xids_cap = XIDS_MIN;   // grown per round (size_exports)
+  HIPCHK(talloc(s, &s->d.xrec, s->d.xrec_cap)); HIPCHK(talloc(s, &s->d.xids, s->d.xids_cap));
+  window_stale(s);
   return KB_OK;
+}
+static int row_fp(kb_sim* s, uint32_t node, uint32_t* fp) {
+  if (ctl_chk_row(s, node)) return KB_INVALID_ARGUMENT;
+  k_fp_one<<<1, 64, 0, s->st>>>(s->d, node);
+  HIPCHK(hipMemcpyAsync(fp, s->d.fp + node, 4, hipMemcpyDeviceToHost, s->st));
+  HIPCHK(hipStreamSynchronize(s->st));
+  return KB_OK;
+}
+static int lat_column(kb_sim* s, uint32_t node, std::vector<uint16_t>& lat) {   // track_latency only
+  if (!s->d.lat) return KB_OK;
+  lat.resize(s->C);
+  k_lat_column<<<(s->C + 255) / 256, 256, 0, s->st>>>(s->d, node, s->lat_col);
+  HIPCHK(hipMemcpyAsync(lat.data(), s->lat_col, 2ull * s->C, hipMemcpyDeviceToHost, s->st));
+  HIPCHK(hipStreamSynchronize(s->st));
+  return KB_OK;
+}
+
+// ---- lifecycle: every shard applies the call to its replicated per-id facts; they take effect at the next round
+extern "C" int kb_sim_start_node(kb_sim* s, uint32_t node) {
+  if (chk(s, node)) return KB_INVALID_ARGUMENT;
+  return route(s, R_ALL, node, [&](auto* e) { return ctl_start_node(e, node); });
+}
+extern "C" int kb_sim_stop_node(kb_sim* s, uint32_t node) {
+  if (chk(s, node)) return KB_INVALID_ARGUMENT;
+  return route(s, R_ALL, node, [&](auto* e) { return ctl_stop_node(e, node); });
+}
+extern "C" int kb_sim_restart_node(kb_sim* s, uint32_t node, uint32_t* new_node) {
+  if (chk(s, node) || !new_node) return KB_INVALID_ARGUMENT;
+  bool first = true;                                 // every shard allocates the same fresh id (replicated counter)
+  return route(s, R_ALL, node, [&](auto* e) -> int {
+    uint32_t to = 0;
+    const int rc = ctl_restart_node(e, node, &to);
+    if (rc) return rc;
+    if (!first && to != *new_node) { seterr("shards allocated different fresh ids"); return KB_IO_ERROR; }
+    *new_node = to; first = false;
+    return KB_OK;
+  });
+}
+extern "C" int kb_sim_is_running(kb_sim* s, uint32_t node, int* running) {
+  if (chk(s, node) || !running) return KB_INVALID_ARGUMENT;
+  return route(s, R_FIRST, node, [&](auto* e) { return ctl_is_running(e, node, running); });
+}
+extern "C" int kb_sim_ping_addrs(kb_sim* s, uint32_t node, const uint32_t* peers, size_t n) {
+  if (chk(s, node) || (n && !peers)) return KB_INVALID_ARGUMENT;
+  return route(s, R_ALL, node, [&](auto* e) { return ctl_ping_addrs(e, node, peers, n); });
+}
+extern "C" int kb_sim_set_identity(kb_sim* s, uint32_t node, const uint8_t* identity, size_t len) {
+  if (chk(s, node) || len > MAXID || (len && !identity)) return KB_INVALID_ARGUMENT;
+  return route(s, R_ALL, node, [&](auto* e) { return ctl_set_identity(e, node, identity, len); });
+}
+extern "C" int kb_sim_identity(kb_sim* s, uint32_t node, uint8_t* buf, size_t cap, size_t* len) {
+  if (chk(s, node) || !len) return KB_INVALID_ARGUMENT;
+  return route(s, R_FIRST, node, [&](auto* e) { return ctl_identity(e, node, buf, cap, len); });   // replicated per id
 }
 // ---- discovery (src/discovery.rs:30-89, src/kaboodle.rs:305-331) ----------------------------------
 extern "C" int kb_sim_probe(kb_sim* s, const kb_wire_addr* prober) {
-  if (s && s->sp) { if (!prober) return KB_INVALID_ARGUMENT; s->sp->probe_q.push_back(*prober); return KB_OK; }
-  SPG_ALL([&](kb_sim* t) { return kb_sim_probe(t, prober); });
   if (!s || !prober) return KB_INVALID_ARGUMENT;
-  GROUP_ALL([&](kb_sim* t) { return kb_sim_probe(t, prober); });
-  s->probe_q.push_back(*prober);
-  return KB_OK;
+  return route(s, R_ALL, 0, [&](auto* e) { e->probe_q.push_back(*prober); return KB_OK; });
 }
 extern "C" int kb_sim_probe_responses(kb_sim* s, kb_probe_response* out, size_t cap, size_t* n) {
-  if (s && s->sp) return n ? sp_probe_responses(s->sp, out, cap, n) : KB_INVALID_ARGUMENT;
   if (!s || !n) return KB_INVALID_ARGUMENT;
-  if (is_group(s)) {                                 // every shard's responders, merged in canonical order
-    std::vector<kb_probe_response> all;
-    for (kb_sim* t : s->shards) {
-      const std::vector<kb_probe_response>& v = t->sp ? t->sp->presp : t->presp;
-      all.insert(all.end(), v.begin(), v.end());
-    }
-    std::stable_sort(all.begin(), all.end(), [](const kb_probe_response& a, const kb_probe_response& b) {
-      return a.round != b.round ? a.round < b.round : a.responder != b.responder ? a.responder < b.responder : a.probe < b.probe;
-    });
-    *n = all.size();
-    if (!out) return KB_OK;
-    if (cap < all.size()) return KB_CAPACITY;
-    if (!all.empty()) memcpy(out, all.data(), all.size() * sizeof(kb_probe_response));
-    for (kb_sim* t : s->shards) { t->presp.clear(); if (t->sp) t->sp->presp.clear(); }
-    return KB_OK;
-  }
-  *n = s->presp.size();
+  std::vector<kb_probe_response> all;                // every shard's responders, merged in canonical order
+  route(s, R_ALL, 0, [&](auto* e) { all.insert(all.end(), e->presp.begin(), e->presp.end()); return KB_OK; });
+  std::stable_sort(all.begin(), all.end(), [](const kb_probe_response& a, const kb_probe_response& b) {
+    return a.round != b.round ? a.round < b.round : a.responder != b.responder ? a.responder < b.responder : a.probe < b.probe;
+  });
+  *n = all.size();
   if (!out) return KB_OK;
-  if (cap < s->presp.size()) return KB_CAPACITY;
-  if (!s->presp.empty()) memcpy(out, s->presp.data(), s->presp.size() * sizeof(kb_probe_response));
-  s->presp.clear();
-  return KB_OK;
+  if (cap < all.size()) return KB_CAPACITY;
+  if (!all.empty()) memcpy(out, all.data(), all.size() * sizeof(kb_probe_response));
+  return route(s, R_ALL, 0, [](auto* e) { e->presp.clear(); return KB_OK; });
 }
 // ---- external peers ------------------------------------------------------------------------
 static_assert(sizeof(XRec) == sizeof(kb_unicast), "XRec mirrors kb_unicast");
 extern "C" int kb_sim_set_external(kb_sim* s, uint32_t node) {
-  if (s && s->sp) return chk(s, node) ? KB_INVALID_ARGUMENT : sp_set_external(s->sp, node);
-  SPG_ALL([&](kb_sim* t) { return kb_sim_set_external(t, node); });
   if (chk(s, node)) return KB_INVALID_ARGUMENT;
-  kb_sim* h = is_group(s) ? s->shards[0] : s;
-  if (h->h_ext.empty()) h->h_ext.assign(s->C, 0);
-  if (h->h_ext[node]) return KB_OK;
-  int ever = 0;
-  { const int rc = ever_bound(h, node, &ever); if (rc) return rc; }
-  if (ever) { seterr("an external peer takes an address no instance has bound"); return KB_INVALID_OPERATION; }
-  auto one = [&](kb_sim* t) -> int {
-    (void)hipSetDevice(t->device);
-    if (t->h_ext.empty()) t->h_ext.assign(t->C, 0);
-    t->h_ext[node] = 1; t->n_ext++;
-    t->h_idset[node] = 1;                            // not a fresh id: churn joins and restarts skip it
-    const uint8_t o = 1;
-    HIPCHK(hipMemcpy(t->d.ext + node, &o, 1, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(t->d.idset + node, &o, 1, hipMemcpyHostToDevice));
-    if (!t->d.xrec) {
-      t->d.xrec_cap = XREC_MIN; t->d.xids_cap = XIDS_MIN;   // grown per round (size_exports)
-      HIPCHK(talloc(t, &t->d.xrec, t->d.xrec_cap)); HIPCHK(talloc(t, &t->d.xids, t->d.xids_cap));
-      t->buf_gen++;                                  // a captured receive window holds the old Dev
-    }
-    return KB_OK;
-  };
-  if (is_group(s)) { for (kb_sim* t : s->shards) { const int rc = one(t); if (rc) return rc; } return KB_OK; }
-  return one(s);
+  return route(s, R_ALL, node, [&](auto* e) { return ctl_set_external(e, node); });
 }
 extern "C" int kb_sim_inject(kb_sim* s, const kb_unicast* m, const uint32_t* ids) {
-  if (s && s->sp) return sp_inject(s->sp, m, ids);
-  SPG_ALL([&](kb_sim* t) { return kb_sim_inject(t, m, ids); });
-  if (!s || !m || m->sender >= s->C || m->dest >= s->C || (m->kind > K_KPR && m->kind != KB_WIRE_JOIN) || (m->pay_len && !ids))
-    return KB_INVALID_ARGUMENT;
-  kb_sim* h = is_group(s) ? s->shards[0] : s;
-  if (h->h_ext.empty() || !h->h_ext[m->sender]) { seterr("kb_sim_inject: the sender is not an external peer"); return KB_INVALID_OPERATION; }
-  if (m->kind == KB_WIRE_JOIN) {                       // a Join broadcast: the next round's Join list
-    if (std::find(h->inj_join.begin(), h->inj_join.end(), m->sender) != h->inj_join.end()) {
-      seterr("kb_sim_inject: one Join per external peer per round"); return KB_CAPACITY;
-    }
-    if (is_group(s)) { for (kb_sim* t : s->shards) t->inj_join.push_back(m->sender); }
-    else s->inj_join.push_back(m->sender);
-    return KB_OK;
-  }
-  if ((m->kind == K_PINGREQ || m->kind == K_ACK) && m->a >= s->C) return KB_INVALID_ARGUMENT;
-  for (uint32_t k = 0; k < m->pay_len; ++k) if (ids[k] >= s->C) return KB_INVALID_ARGUMENT;
-  uint32_t per = 0, rel = 0;
-  for (const XRec& x : h->inj) if (x.sender == m->sender) { per++; if (x.kind == K_KP) rel += x.pay_len; }
-  if (per >= (uint32_t)TICK_MAX) { seterr("kb_sim_inject: 33 records per external peer per round"); return KB_CAPACITY; }
-  auto one = [&](kb_sim* t) -> int {
-    XRec x{0, 0, m->sender, m->dest, 0, m->kind, m->kind == K_KP ? 0u : m->a, m->fp, m->n, (uint32_t)t->inj_ids.size(),
-           m->kind == K_KP ? m->pay_len : 0u, rel};
-    if (m->kind == K_KP) t->inj_ids.insert(t->inj_ids.end(), ids, ids + m->pay_len);
-    t->inj.push_back(x);
-    return KB_OK;
-  };
-  if (is_group(s)) { for (kb_sim* t : s->shards) one(t); return KB_OK; }
-  return one(s);
+  if (!s || !m) return KB_INVALID_ARGUMENT;
+  return route(s, R_ALL, 0, [&](auto* e) { return ctl_inject(e, m, ids); });
 }
 extern "C" int kb_sim_exported(kb_sim* s, kb_unicast* out, size_t cap, size_t* n, uint32_t* ids, size_t cap_ids, size_t* n_ids) {
-  if (s && s->sp) return (!n || !n_ids) ? KB_INVALID_ARGUMENT : sp_exported(s->sp, out, cap, n, ids, cap_ids, n_ids);
   if (!s || !n || !n_ids) return KB_INVALID_ARGUMENT;
   std::vector<kb_unicast> all;
   std::vector<uint32_t> all_ids;
-  const std::vector<kb_sim*> hs = is_group(s) ? s->shards : std::vector<kb_sim*>{s};
-  for (kb_sim* t : hs)
-    for (const kb_unicast& u : (t->sp ? t->sp->xq : t->xq)) {
-      const std::vector<uint32_t>& xi = t->sp ? t->sp->xq_ids : t->xq_ids;
+  route(s, R_ALL, 0, [&](auto* e) {
+    for (const kb_unicast& u : e->xq) {
       kb_unicast v = u;
       v.pay_off = (uint32_t)all_ids.size();
-      all_ids.insert(all_ids.end(), xi.begin() + u.pay_off, xi.begin() + u.pay_off + u.pay_len);
+      all_ids.insert(all_ids.end(), e->xq_ids.begin() + u.pay_off, e->xq_ids.begin() + u.pay_off + u.pay_len);
       std::sort(all_ids.begin() + v.pay_off, all_ids.end());   // a KnownPeers map has no order: ascending ids
       all.push_back(v);
     }
+    return KB_OK;
+  });
   std::stable_sort(all.begin(), all.end(), [](const kb_unicast& a, const kb_unicast& b) {
     return a.round != b.round ? a.round < b.round : a.wave != b.wave ? a.wave < b.wave : a.sender != b.sender ? a.sender < b.sender
                                                                                        : a.seq < b.seq; });
@@ -1980,59 +1805,19 @@ extern "C" int kb_sim_exported(kb_sim* s, kb_unicast* out, size_t cap, size_t* n
   if (cap < all.size() || (!all_ids.empty() && (!ids || cap_ids < all_ids.size()))) { seterr("export buffer too small"); return KB_CAPACITY; }
   if (!all.empty()) memcpy(out, all.data(), all.size() * sizeof(kb_unicast));
   if (!all_ids.empty()) memcpy(ids, all_ids.data(), 4 * all_ids.size());
-  for (kb_sim* t : hs) { t->xq.clear(); t->xq_ids.clear(); if (t->sp) { t->sp->xq.clear(); t->sp->xq_ids.clear(); } }
-  return KB_OK;
+  return route(s, R_ALL, 0, [](auto* e) { e->xq.clear(); e->xq_ids.clear(); return KB_OK; });
 }
 
-// the last round's Join / Failed broadcasts (whole mesh; sender order, a node's Join before its Failed)
 extern "C" int kb_sim_broadcasts(kb_sim* s, kb_broadcast* out, size_t cap, size_t* n) {
-  if (s && s->sp) return n ? sp_broadcasts(s->sp, out, cap, n) : KB_INVALID_ARGUMENT;
-  SPG_FIRST([&](kb_sim* t) { return kb_sim_broadcasts(t, out, cap, n); });
   if (!s || !n) return KB_INVALID_ARGUMENT;
-  if (is_group(s)) return kb_sim_broadcasts(s->shards[0], out, cap, n);   // every shard holds the lists
-  std::vector<BCast> j(s->nj), f(s->nf);
-  if (s->nj) HIPCHK(hipMemcpy(j.data(), s->bjoin, sizeof(BCast) * s->nj, hipMemcpyDeviceToHost));
-  if (s->nf) HIPCHK(hipMemcpy(f.data(), s->bfail, sizeof(BCast) * s->nf, hipMemcpyDeviceToHost));
-  size_t c = 0, a = 0, b = 0;
-  while (a < j.size() || b < f.size()) {
-    const bool tj = b == f.size() || (a < j.size() && j[a].sender <= f[b].sender);
-    if (out && c < cap) {
-      kb_broadcast& o = out[c];
-      memset(&o, 0, sizeof o);
-      if (tj) { o.kind = KB_WIRE_JOIN; o.sender = j[a].sender; o.peer = j[a].peer; }
-      else { o.kind = KB_WIRE_FAILED; o.sender = f[b].sender; o.peer = f[b].peer; }
-    }
-    if (tj) a++; else b++;
-    c++;
-  }
-  *n = c;
-  return (out && cap < c) ? KB_CAPACITY : KB_OK;
+  return route(s, R_FIRST, 0, [&](auto* e) { return ctl_broadcasts(e, out, cap, n); });   // every shard holds the lists
 }
 extern "C" int kb_sim_fingerprint(kb_sim* s, uint32_t node, uint32_t* fp) {
-  if (s && s->sp) return (chk(s, node) || !fp) ? KB_INVALID_ARGUMENT : sp_fingerprint(s->sp, node, fp);
-  SPG_OWNER(node, [&](kb_sim* t) { return kb_sim_fingerprint(t, node, fp); });
   if (chk(s, node) || !fp) return KB_INVALID_ARGUMENT;
-  GROUP_OWNER(node, [&](kb_sim* t) { return kb_sim_fingerprint(t, node, fp); });
-  if (chk_row(s, node)) return KB_INVALID_ARGUMENT;
-  k_fp_one<<<1, 64, 0, s->st>>>(s->d, node);
-  HIPCHK(hipMemcpyAsync(fp, s->d.fp + node, 4, hipMemcpyDeviceToHost, s->st));
-  HIPCHK(hipStreamSynchronize(s->st));
-  return KB_OK;
+  return route(s, R_OWNER, node, [&](auto* e) { return row_fp(e, node, fp); });
 }
-// all ids; 0 for non-running ids and (sharded ranks) for rows held by other shards
-extern "C" int kb_sim_fingerprints(kb_sim* s, uint32_t* fps, size_t cap) {
-  if (s && s->sp) return (!fps || cap < s->C) ? KB_INVALID_ARGUMENT : sp_fingerprints(s->sp, fps);
-  if (!s || !fps || cap < s->C) return KB_INVALID_ARGUMENT;
-  if (is_group(s)) {
-    std::vector<uint32_t> part(s->C);
-    memset(fps, 0, 4ull * s->C);
-    for (kb_sim* t : s->shards) {
-      const int rc = kb_sim_fingerprints(t, part.data(), part.size());
-      if (rc) return rc;
-      for (uint32_t j = t->lo; j < t->hi; ++j) fps[j] = part[j];
-    }
-    return KB_OK;
-  }
+// all ids; 0 for non-running ids and for rows held by other shards
+static int eng_fingerprints(kb_sim* s, uint32_t* fps) {
   k_fp_all<<<(s->R + 3) / 4, 256, 0, s->st>>>(s->d);
   std::vector<uint8_t> al(s->C);
   memset(fps, 0, 4ull * s->C);
@@ -2042,11 +1827,18 @@ extern "C" int kb_sim_fingerprints(kb_sim* s, uint32_t* fps, size_t cap) {
   for (uint32_t i = 0; i < s->C; ++i) if (!al[i]) fps[i] = 0;
   return KB_OK;
 }
-extern "C" int kb_sim_true_fingerprint(kb_sim* s, uint32_t* fp) {
-  if (s && s->sp) return fp ? sp_true_fingerprint(s->sp, fp) : KB_INVALID_ARGUMENT;
-  SPG_FIRST([&](kb_sim* t) { return kb_sim_true_fingerprint(t, fp); });
-  if (!s || !fp) return KB_INVALID_ARGUMENT;
-  if (is_group(s)) return kb_sim_true_fingerprint(s->shards[0], fp);
+extern "C" int kb_sim_fingerprints(kb_sim* s, uint32_t* fps, size_t cap) {
+  if (!s || !fps || cap < s->C) return KB_INVALID_ARGUMENT;
+  if (!is_group(s)) return visit(s, [&](auto* e) { return eng_fingerprints(e, fps); });
+  std::vector<uint32_t> part(s->C);
+  memset(fps, 0, 4ull * s->C);
+  return route(s, R_ALL, 0, [&](auto* e) {
+    const int rc = eng_fingerprints(e, part.data());
+    for (uint32_t j = e->lo; !rc && j < e->hi; ++j) fps[j] = part[j];
+    return rc;
+  });
+}
+static int eng_true_fingerprint(kb_sim* s, uint32_t* fp) {
   k_alive_bits<<<(s->d.NWR + 255) / 256, 256, 0, s->st>>>(s->d);
   k_truefp_part<<<TRUEFP_G, 256, 0, s->st>>>(s->d, s->d.tfpart);
   k_truefp_fin<<<1, 64, 0, s->st>>>(s->d, s->d.tfpart);
@@ -2055,97 +1847,31 @@ extern "C" int kb_sim_true_fingerprint(kb_sim* s, uint32_t* fp) {
   HIPCHK(hipStreamSynchronize(s->st));
   return KB_OK;
 }
+extern "C" int kb_sim_true_fingerprint(kb_sim* s, uint32_t* fp) {
+  if (!s || !fp) return KB_INVALID_ARGUMENT;
+  return route(s, R_FIRST, 0, [&](auto* e) { return eng_true_fingerprint(e, fp); });
+}
 extern "C" int kb_sim_dump_row(kb_sim* s, uint32_t node, uint8_t* rw, size_t cap) {
-  SPG_OWNER(node, [&](kb_sim* t) { return kb_sim_dump_row(t, node, rw, cap); });
-  if (s && s->sp) {
-    if (chk(s, node) || !rw || cap < s->C) return KB_INVALID_ARGUMENT;
+  if (chk(s, node) || !rw || cap < s->C) return KB_INVALID_ARGUMENT;
+  return route(s, R_OWNER, node, [&](auto* e) {
     std::vector<uint8_t> v;
-    const int rc = sp_read_row(s->sp, node, v);
+    int rc = ctl_chk_row(e, node);
+    if (!rc) rc = read_row(e, node, v);
     if (!rc) memcpy(rw, v.data(), s->C);
     return rc;
-  }
-  if (chk(s, node) || !rw || cap < s->C) return KB_INVALID_ARGUMENT;
-  GROUP_OWNER(node, [&](kb_sim* t) { return kb_sim_dump_row(t, node, rw, cap); });
-  if (chk_row(s, node)) return KB_INVALID_ARGUMENT;
-  std::vector<uint8_t> v;
-  int rc = read_row(s, node, v);
-  if (rc) return rc;
-  memcpy(rw, v.data(), s->C);
-  return KB_OK;
+  });
 }
 extern "C" int kb_sim_peers(kb_sim* s, uint32_t node, uint32_t* peers, size_t cap, size_t* n) {
-  SPG_OWNER(node, [&](kb_sim* t) { return kb_sim_peers(t, node, peers, cap, n); });
-  if (s && s->sp) {
-    if (chk(s, node) || !n) return KB_INVALID_ARGUMENT;
-    std::vector<uint8_t> rw;
-    const int rc = sp_read_row(s->sp, node, rw);
-    if (rc) return rc;
-    size_t c = 0;
-    for (uint32_t j = 0; j < s->C; ++j) if (rw[j]) { if (peers && c < cap) peers[c] = j; c++; }
-    *n = c;
-    return (peers && cap < c) ? KB_CAPACITY : KB_OK;
-  }
   if (chk(s, node) || !n) return KB_INVALID_ARGUMENT;
-  GROUP_OWNER(node, [&](kb_sim* t) { return kb_sim_peers(t, node, peers, cap, n); });
-  if (chk_row(s, node)) return KB_INVALID_ARGUMENT;
-  std::vector<uint8_t> rw;
-  int rc = read_row(s, node, rw);
-  if (rc) return rc;
-  size_t c = 0;
-  for (uint32_t j = 0; j < s->C; ++j) if (rw[j]) { if (peers && c < cap) peers[c] = j; c++; }
-  *n = c;
-  return (peers && cap < c) ? KB_CAPACITY : KB_OK;
+  return route(s, R_OWNER, node, [&](auto* e) { return ctl_peers(e, node, peers, cap, n); });
 }
 extern "C" int kb_sim_peer_states(kb_sim* s, uint32_t node, kb_peer_state* out, size_t cap, size_t* n) {
-  if (s && s->sp) return (chk(s, node) || !n) ? KB_INVALID_ARGUMENT : sp_peer_states(s->sp, node, out, cap, n);
-  SPG_OWNER(node, [&](kb_sim* t) { return kb_sim_peer_states(t, node, out, cap, n); });
   if (chk(s, node) || !n) return KB_INVALID_ARGUMENT;
-  GROUP_OWNER(node, [&](kb_sim* t) { return kb_sim_peer_states(t, node, out, cap, n); });
-  if (chk_row(s, node)) return KB_INVALID_ARGUMENT;
-  std::vector<uint8_t> rw;
-  int rc = read_row(s, node, rw);
-  if (rc) return rc;
-  std::vector<Susp> sl(SLOTS);
-  HIPCHK(hipMemcpy(sl.data(), s->d.susp + (size_t)node * SLOTS, sizeof(Susp) * SLOTS, hipMemcpyDeviceToHost));
-  std::vector<uint16_t> lat;
-  if (s->d.lat) {
-    lat.resize(s->C);
-    k_lat_column<<<(s->C + 255) / 256, 256, 0, s->st>>>(s->d, node, s->lat_col);
-    HIPCHK(hipMemcpyAsync(lat.data(), s->lat_col, 2ull * s->C, hipMemcpyDeviceToHost, s->st));
-    HIPCHK(hipStreamSynchronize(s->st));
-  }
-  const int32_t E = epoch_base(s->round > 0 ? s->round - 1 : 0);
-  size_t c = 0;
-  for (uint32_t j = 0; j < s->C; ++j) {
-    if (!rw[j]) continue;
-    if (out && c < cap) {
-      kb_peer_state& o = out[c];
-      memset(&o, 0, sizeof o);
-      o.peer = j;
-      o.identity_len = s->h_idlen[j];
-      memcpy(o.identity, &s->h_ident[(size_t)j * MAXID], s->h_idlen[j]);
-      o.latency_ms = !lat.empty() && lat[j] != LAT_NONE ? lat[j] : KB_LATENCY_NONE;
-      if (rw[j] == ST_SUSPECT) {
-        const Susp* q = nullptr;
-        for (auto& x : sl) if (x.kind && x.peer == j) q = &x;
-        o.state = q && q->kind == SK_WFIP ? KB_STATE_WAITING_FOR_INDIRECT_PING : KB_STATE_WAITING_FOR_PING;
-        o.since = q ? q->since : 0;
-      } else {
-        o.state = KB_STATE_KNOWN;
-        o.since = rw[j] == ST_ANCIENT ? INT32_MIN : (int32_t)rw[j] + E - EOFF;
-      }
-    }
-    c++;
-  }
-  *n = c;
-  return (out && cap < c) ? KB_CAPACITY : KB_OK;
+  return route(s, R_OWNER, node, [&](auto* e) { return ctl_peer_states(e, node, out, cap, n); });
 }
-extern "C" int kb_sim_watch(kb_sim* s, uint32_t node) {
-  if (s && s->sp) return chk(s, node) ? KB_INVALID_ARGUMENT : sp_watch(s->sp, node);
-  SPG_OWNER(node, [&](kb_sim* t) { return kb_sim_watch(t, node); });
-  if (chk(s, node)) return KB_INVALID_ARGUMENT;
-  GROUP_OWNER(node, [&](kb_sim* t) { return kb_sim_watch(t, node); });
-  if (chk_row(s, node)) return KB_INVALID_ARGUMENT;
+// ---- event observers: a device snapshot here, a host snapshot on the sparse rows (eng_watch, eng_events) -------
+static int eng_watch(kb_sim* s, uint32_t node) {
+  if (ctl_chk_row(s, node)) return KB_INVALID_ARGUMENT;
   for (uint32_t w : s->watch_node) if (w == node) return KB_OK;      // one observer per node
   if (!s->ev_out) HIPCHK(talloc(s, &s->ev_out, 2ull * s->C + 4));
   uint32_t* snap = nullptr;
@@ -2155,18 +1881,13 @@ extern "C" int kb_sim_watch(kb_sim* s, uint32_t node) {
   s->watch_node.push_back(node); s->watch_fp.push_back(0); s->watch_snap.push_back(snap);
   return KB_OK;
 }
-extern "C" int kb_sim_events(kb_sim* s, uint32_t node, uint32_t* discovered, size_t cap_d, size_t* n_d,
-                             uint32_t* departed, size_t cap_p, size_t* n_p, uint32_t* fp, int* fp_changed) {
-  SPG_OWNER(node, [&](kb_sim* t) {
-    return kb_sim_events(t, node, discovered, cap_d, n_d, departed, cap_p, n_p, fp, fp_changed); });
-  if (s && s->sp) {
-    if (chk(s, node) || !n_d || !n_p || !fp || !fp_changed) return KB_INVALID_ARGUMENT;
-    return sp_events(s->sp, node, discovered, cap_d, n_d, departed, cap_p, n_p, fp, fp_changed);
-  }
-  if (chk(s, node) || !n_d || !n_p || !fp || !fp_changed) return KB_INVALID_ARGUMENT;
-  GROUP_OWNER(node, [&](kb_sim* t) {
-    return kb_sim_events(t, node, discovered, cap_d, n_d, departed, cap_p, n_p, fp, fp_changed); });
-  if (chk_row(s, node)) return KB_INVALID_ARGUMENT;
+extern "C" int kb_sim_watch(kb_sim* s, uint32_t node) {
+  if (chk(s, node)) return KB_INVALID_ARGUMENT;
+  return route(s, R_OWNER, node, [&](auto* e) { return eng_watch(e, node); });
+}
+static int eng_events(kb_sim* s, uint32_t node, uint32_t* discovered, size_t cap_d, size_t* n_d, uint32_t* departed,
+                      size_t cap_p, size_t* n_p, uint32_t* fp, int* fp_changed) {
+  if (ctl_chk_row(s, node)) return KB_INVALID_ARGUMENT;
   size_t k = 0;
   while (k < s->watch_node.size() && s->watch_node[k] != node) ++k;
   if (k == s->watch_node.size()) { seterr("node is not watched (kb_sim_watch)"); return KB_INVALID_OPERATION; }
@@ -2192,6 +1913,12 @@ extern "C" int kb_sim_events(kb_sim* s, uint32_t node, uint32_t* discovered, siz
   if (*fp_changed) s->watch_fp[k] = *fp;
   return KB_OK;
 }
+extern "C" int kb_sim_events(kb_sim* s, uint32_t node, uint32_t* discovered, size_t cap_d, size_t* n_d,
+                             uint32_t* departed, size_t cap_p, size_t* n_p, uint32_t* fp, int* fp_changed) {
+  if (chk(s, node) || !n_d || !n_p || !fp || !fp_changed) return KB_INVALID_ARGUMENT;
+  return route(s, R_OWNER, node, [&](auto* e) {
+    return eng_events(e, node, discovered, cap_d, n_d, departed, cap_p, n_p, fp, fp_changed); });
+}
 // the per-workgroup partial counters (d.sacc) folded into d.stats; the stream is idle afterwards
 __global__ __launch_bounds__(256) void k_stats_fold(Dev d) {
   const uint32_t k = blockIdx.x;                   // one counter per workgroup
@@ -2204,131 +1931,44 @@ __global__ __launch_bounds__(256) void k_stats_fold(Dev d) {
   if (threadIdx.x == 0 && t) d.stats[k] += t;
 }
 static int fold_stats(kb_sim* s) {
-  if (is_group(s)) { for (kb_sim* t : s->shards) { const int rc = fold_stats(t); if (rc) return rc; } return KB_OK; }
   (void)hipSetDevice(s->device);
   k_stats_fold<<<NSTAT, 256, 0, s->st>>>(s->d);
   HIPCHK(hipStreamSynchronize(s->st));
   return KB_OK;
 }
+// the counters summed over the shards (a rank handle: over the mesh, a collective), replicated facts from one
 extern "C" int kb_sim_stats(kb_sim* s, kb_stats* out) {
-  if (s && s->sp) return out ? sp_stats_out(s->sp, out) : KB_INVALID_ARGUMENT;
-  if (sp_grp(s)) {                                   // the counters summed over the shards, replicated facts from one
-    if (!out) return KB_INVALID_ARGUMENT;
-    unsigned long long st[NSTAT] = {0};
-    for (kb_sim* t : s->shards) {
-      unsigned long long v[NSTAT];
-      const int rc = sp_read_stats(t->sp, v);
-      if (rc) return rc;
-      for (int k = 0; k < NSTAT; ++k) st[k] += v[k];
-    }
-    return sp_stats_fill(s->shards[0]->sp, st, out);
-  }
   if (!s || !out) return KB_INVALID_ARGUMENT;
-  { const int rc = fold_stats(s); if (rc) return rc; }
-  unsigned long long st[NSTAT];
-  uint32_t ctr[NCTR];
-  kb_sim* h = is_group(s) ? s->shards[0] : s;       // replicated facts come from any shard
-  if (is_group(s)) {
-    memset(st, 0, sizeof st);
-    for (kb_sim* t : s->shards) {
-      unsigned long long v[NSTAT];
-      HIPCHK(hipMemcpy(v, t->d.stats, sizeof v, hipMemcpyDeviceToHost));
-      for (int k = 0; k < NSTAT; ++k) st[k] += v[k];
-    }
-  } else if (s->xf && !s->in_group) {               // ranks: the counters summed over the mesh
-    HIPCHK(hipMemcpyAsync(s->xstats, s->d.stats, sizeof st, hipMemcpyDeviceToDevice, s->st));
-    if (!s->xf->allreduce_sum_u64(s->xstats, NSTAT, s->st)) { seterr(s->xf->error()); return KB_IO_ERROR; }
-    HIPCHK(hipMemcpyAsync(st, s->xstats, sizeof st, hipMemcpyDeviceToHost, s->st));
-    HIPCHK(hipStreamSynchronize(s->st));
-  } else {
-    HIPCHK(hipMemcpy(st, s->d.stats, sizeof st, hipMemcpyDeviceToHost));
-  }
-  HIPCHK(hipMemcpy(ctr, h->d.ctr, sizeof ctr, hipMemcpyDeviceToHost));
-  std::vector<uint8_t> al(h->C);
-  HIPCHK(hipMemcpy(al.data(), h->d.alive, h->C, hipMemcpyDeviceToHost));
-  memset(out, 0, sizeof *out);
-  out->round = h->round;
-  uint32_t a = 0;
-  for (uint8_t x : al) a += x;
-  out->alive = a;
-  out->agree = ctr[C_LASTAGREE];
-  out->first_converged_round = (int32_t)ctr[C_FIRSTCONV];
-  out->last_converged_round = (int32_t)ctr[C_LASTCONV];
-  out->next_free_id = ctr[C_NEXTFREE];
-  out->sent_ping = st[S_PING]; out->sent_ping_req = st[S_PINGREQ]; out->sent_ack = st[S_ACK];
-  out->sent_known_peers = st[S_KP]; out->sent_kpr = st[S_KPR];
-  out->bcast_join = h->bj_total; out->bcast_failed = h->bf_total;
-  out->drop_dead = st[S_DEAD]; out->drop_loss = st[S_LOSS]; out->drop_window = st[S_WINDOW];
-  out->drop_oversize = st[S_OVERSIZE]; out->drop_partition = st[S_PART]; out->drop_bcast = st[S_BDROP];
-  out->removed_timeout = st[S_RMTIMEOUT]; out->removed_failed = st[S_RMFAILED]; out->join_responses = st[S_JRESP];
-  out->curious_overflow = st[S_CUROVF]; out->churn_leaves = st[S_CLEAVE]; out->churn_joins = st[S_CJOIN];
-  out->sent_kp_ids = st[S_KPIDS];
-  out->alive_rounds = st[S_ALIVER];
-  out->probe_responses = st[S_PROBERESP];
-  out->exported = st[S_EXPORT];
-  return KB_OK;
+  unsigned long long st[NSTAT] = {0};
+  const int rc = route(s, R_ALL, 0, [&](auto* e) {
+    unsigned long long v[NSTAT];
+    const int rc = ctl_read_stats(e, v);
+    for (int k = 0; !rc && k < NSTAT; ++k) st[k] += v[k];
+    return rc;
+  });
+  return rc ? rc : route(s, R_FIRST, 0, [&](auto* e) { return ctl_stats_fill(e, st, out); });
 }
 // per id: alive, n, last_bcast, start_round; n and last_bcast only for the rows this handle holds
 extern "C" int kb_sim_dump_scalars(kb_sim* s, int32_t* out, size_t cap) {
-  if (s && s->sp) return (!out || cap < 4ull * s->C) ? KB_INVALID_ARGUMENT : sp_dump_scalars(s->sp, out);
   if (!s || !out || cap < 4ull * s->C) return KB_INVALID_ARGUMENT;
-  if (is_group(s)) {
-    std::vector<int32_t> part(4ull * s->C);
-    for (kb_sim* t : s->shards) {
-      const int rc = kb_sim_dump_scalars(t, part.data(), part.size());
-      if (rc) return rc;
-      for (uint32_t i = 0; i < s->C; ++i)
-        if ((i >= t->lo && i < t->hi) || t == s->shards[0]) memcpy(out + 4 * i, part.data() + 4 * i, 16);
-    }
-    return KB_OK;
-  }
-  std::vector<uint8_t> al(s->C);
-  std::vector<uint32_t> n(s->R);
-  std::vector<int32_t> lb(s->R), sr(s->C);
-  HIPCHK(hipMemcpy(al.data(), s->d.alive, s->C, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(n.data(), L(s, s->d.n), 4ull * s->R, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(lb.data(), L(s, s->d.last_bcast), 4ull * s->R, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(sr.data(), s->d.start_round, 4ull * s->C, hipMemcpyDeviceToHost));
-  for (uint32_t i = 0; i < s->C; ++i) {
-    const bool loc = i >= s->lo && i < s->hi;
-    out[4 * i] = al[i]; out[4 * i + 1] = loc ? (int32_t)n[i - s->lo] : 0;
-    out[4 * i + 2] = loc ? lb[i - s->lo] : 0; out[4 * i + 3] = sr[i];
-  }
-  return KB_OK;
+  if (!is_group(s)) return visit(s, [&](auto* e) { return ctl_dump_scalars(e, out); });
+  std::vector<int32_t> part(4ull * s->C);
+  bool first = true;                                 // the per-id facts from the first shard, each row's from its shard
+  return route(s, R_ALL, 0, [&](auto* e) {
+    const int rc = ctl_dump_scalars(e, part.data());
+    for (uint32_t i = 0; !rc && i < s->C; ++i)
+      if ((i >= e->lo && i < e->hi) || first) memcpy(out + 4 * i, part.data() + 4 * i, 16);
+    first = false;
+    return rc;
+  });
 }
 extern "C" int kb_sim_dump_suspects(kb_sim* s, uint32_t node, int32_t* out, size_t cap, size_t* n) {
-  if (s && s->sp) return (chk(s, node) || !n) ? KB_INVALID_ARGUMENT : sp_dump_suspects(s->sp, node, out, cap, n);
-  SPG_OWNER(node, [&](kb_sim* t) { return kb_sim_dump_suspects(t, node, out, cap, n); });
   if (chk(s, node) || !n) return KB_INVALID_ARGUMENT;
-  GROUP_OWNER(node, [&](kb_sim* t) { return kb_sim_dump_suspects(t, node, out, cap, n); });
-  if (chk_row(s, node)) return KB_INVALID_ARGUMENT;
-  Susp sl[SLOTS];
-  HIPCHK(hipMemcpy(sl, s->d.susp + (size_t)node * SLOTS, sizeof sl, hipMemcpyDeviceToHost));
-  std::vector<std::array<int32_t, 3>> v;
-  for (auto& x : sl) if (x.kind) v.push_back({(int32_t)x.peer, x.kind, x.since});
-  std::sort(v.begin(), v.end());
-  *n = v.size();
-  if (out) { if (cap < 3 * v.size()) return KB_CAPACITY; for (size_t k = 0; k < v.size(); ++k) memcpy(out + 3 * k, v[k].data(), 12); }
-  return KB_OK;
+  return route(s, R_OWNER, node, [&](auto* e) { return ctl_dump_suspects(e, node, out, cap, n); });
 }
 extern "C" int kb_sim_dump_curious(kb_sim* s, uint32_t node, int32_t* out, size_t cap, size_t* n) {
-  if (s && s->sp) return (chk(s, node) || !n) ? KB_INVALID_ARGUMENT : sp_dump_curious(s->sp, node, out, cap, n);
-  SPG_OWNER(node, [&](kb_sim* t) { return kb_sim_dump_curious(t, node, out, cap, n); });
   if (chk(s, node) || !n) return KB_INVALID_ARGUMENT;
-  GROUP_OWNER(node, [&](kb_sim* t) { return kb_sim_dump_curious(t, node, out, cap, n); });
-  if (chk_row(s, node)) return KB_INVALID_ARGUMENT;
-  Cur cu[CSLOTS];
-  HIPCHK(hipMemcpy(cu, s->d.cur + (size_t)node * CSLOTS, sizeof cu, hipMemcpyDeviceToHost));
-  std::vector<std::array<int32_t, 6>> v;
-  for (auto& x : cu) if (x.used) {
-    std::array<int32_t, 6> e{(int32_t)x.peer, (int32_t)x.nobs, -1, -1, -1, -1};
-    for (uint32_t q = 0; q < x.nobs && q < NOBS; ++q) e[2 + q] = (int32_t)x.obs[q];
-    v.push_back(e);
-  }
-  std::sort(v.begin(), v.end(), [](const std::array<int32_t, 6>& a, const std::array<int32_t, 6>& b) { return a[0] < b[0]; });
-  *n = v.size();
-  if (out) { if (cap < 6 * v.size()) return KB_CAPACITY; for (size_t k = 0; k < v.size(); ++k) memcpy(out + 6 * k, v[k].data(), 24); }
-  return KB_OK;
+  return route(s, R_OWNER, node, [&](auto* e) { return ctl_dump_curious(e, node, out, cap, n); });
 }
 extern "C" uint32_t kb_fingerprint_of_set(const uint32_t* ids, size_t n, const uint8_t* identities, size_t id_stride,
                                           const uint8_t* id_lens) {
@@ -2344,6 +1984,7 @@ extern "C" uint32_t kb_fingerprint_of_set(const uint32_t* ids, size_t n, const u
   }
   return reg ^ 0xFFFFFFFFu;
 }
+// ---- kernel profile: per engine; a group answers with its first shard's (this handle's rows) --------------------
 static int kt_kid(int kind) {
   return kind == KB_KT_ROWPASS ? KI_ROWPASS : kind == KB_KT_FOLD ? KI_FOLD : kind == KB_KT_RESP ? KI_RESP_WAVE
        : kind == KB_KT_PROC ? KI_PROC : -1;
@@ -2354,10 +1995,7 @@ static void prof_flush(kb_sim* s) {
   if (s->st) (void)hipStreamSynchronize(s->st);
   prof_resolve(s, s->krec.size());
 }
-extern "C" int kb_sim_kernel_time(kb_sim* s, int kind, double* ms, uint64_t* launches) {
-  if (s && s->sp) return (!ms || !launches) ? KB_INVALID_ARGUMENT : sp_kernel_time(s->sp, kind, ms, launches);
-  if (!s || !ms || !launches) return KB_INVALID_ARGUMENT;
-  if (is_group(s)) return kb_sim_kernel_time(s->shards[0], kind, ms, launches);
+static int eng_kernel_time(kb_sim* s, int kind, double* ms, uint64_t* launches) {
   prof_flush(s);
   if (kind == KB_KT_ROUND) { *ms = s->round_ms; *launches = s->round_launches; return KB_OK; }
   const int k = kt_kid(kind);
@@ -2365,16 +2003,17 @@ extern "C" int kb_sim_kernel_time(kb_sim* s, int kind, double* ms, uint64_t* lau
   *ms = s->k_ms[k]; *launches = s->k_n[k];
   return KB_OK;
 }
+extern "C" int kb_sim_kernel_time(kb_sim* s, int kind, double* ms, uint64_t* launches) {
+  if (!s || !ms || !launches) return KB_INVALID_ARGUMENT;
+  return route(s, R_FIRST, 0, [&](auto* e) { return eng_kernel_time(e, kind, ms, launches); });
+}
 static uint64_t stat_counter(kb_sim* s, int idx) {
   unsigned long long v = 0;
   if (fold_stats(s)) return 0;
   if (hipMemcpy(&v, s->d.stats + idx, 8, hipMemcpyDeviceToHost) != hipSuccess) return 0;
   return v;
 }
-extern "C" int kb_sim_reset_kernel_time(kb_sim* s) {
-  if (s && s->sp) return sp_reset_kernel_time(s->sp);
-  if (!s) return KB_INVALID_ARGUMENT;
-  GROUP_ALL(kb_sim_reset_kernel_time);
+static int eng_reset_kernel_time(kb_sim* s) {
   prof_flush(s);
   s->round_ms = 0; s->round_launches = 0;
   memset(s->k_ms, 0, sizeof s->k_ms); memset(s->k_wms, 0, sizeof s->k_wms); memset(s->k_n, 0, sizeof s->k_n);
@@ -2384,32 +2023,29 @@ extern "C" int kb_sim_reset_kernel_time(kb_sim* s) {
   }
   return KB_OK;
 }
-// algorithmic bytes a kernel moved since the last reset, counted in-kernel; this handle's
-// rows: shard 0's for a group, like kb_sim_kernel_time
-extern "C" int kb_sim_kernel_bytes(kb_sim* s, int kind, uint64_t* bytes) {
-  if (s && s->sp) { if (!bytes) return KB_INVALID_ARGUMENT; *bytes = 0; return KB_INVALID_ARGUMENT; }
-  SPG_FIRST([&](kb_sim* t) { return kb_sim_kernel_bytes(t, kind, bytes); });
-  if (!s || !bytes) return KB_INVALID_ARGUMENT;
-  if (is_group(s)) return kb_sim_kernel_bytes(s->shards[0], kind, bytes);
+extern "C" int kb_sim_reset_kernel_time(kb_sim* s) {
+  if (!s) return KB_INVALID_ARGUMENT;
+  return route(s, R_ALL, 0, [](auto* e) { return eng_reset_kernel_time(e); });
+}
+// algorithmic bytes a kernel moved since the last reset, counted in-kernel; the sparse rows count none
+static int eng_kernel_bytes(kb_sim* s, int kind, uint64_t* bytes) {
   const int k = kt_kid(kind), b = k < 0 ? -1 : kbytes_stat(k);
   if (b < 0) return KB_INVALID_ARGUMENT;
   *bytes = stat_counter(s, b) - s->k_bytes0[b];
   return KB_OK;
 }
+static int eng_kernel_bytes(SpSim*, int, uint64_t* bytes) { *bytes = 0; return KB_INVALID_ARGUMENT; }
+extern "C" int kb_sim_kernel_bytes(kb_sim* s, int kind, uint64_t* bytes) {
+  if (!s || !bytes) return KB_INVALID_ARGUMENT;
+  return route(s, R_FIRST, 0, [&](auto* e) { return eng_kernel_bytes(e, kind, bytes); });
+}
 extern "C" int kb_sim_set_profiling(kb_sim* s, int level) {
-  if (s && s->sp) { if (level < 0 || level > 2) return KB_INVALID_ARGUMENT; s->sp->prof_level = level; return KB_OK; }
-  SPG_ALL([&](kb_sim* t) { return kb_sim_set_profiling(t, level); });
   if (!s || level < 0 || level > 2) return KB_INVALID_ARGUMENT;
-  GROUP_ALL([&](kb_sim* t) { return kb_sim_set_profiling(t, level); });
-  s->prof_level = level;
-  return KB_OK;
+  return route(s, R_ALL, 0, [&](auto* e) { e->prof_level = level; return KB_OK; });
 }
 // every kernel the rounds launched since the last reset: HIP-event time (sum and per delivery wave),
 // launches, algorithmic bytes where counted in-kernel; kernels never launched are omitted
-extern "C" int kb_sim_kernel_breakdown(kb_sim* s, kb_kernel_time* out, size_t cap, size_t* n) {
-  if (s && s->sp) return n ? sp_kernel_breakdown(s->sp, out, cap, n) : KB_INVALID_ARGUMENT;
-  if (!s || !n) return KB_INVALID_ARGUMENT;
-  if (is_group(s)) return kb_sim_kernel_breakdown(s->shards[0], out, cap, n);
+static int eng_kernel_breakdown(kb_sim* s, kb_kernel_time* out, size_t cap, size_t* n) {
   prof_flush(s);
   size_t c = 0;
   for (int k = 0; k < NKI; ++k) {
@@ -2429,78 +2065,75 @@ extern "C" int kb_sim_kernel_breakdown(kb_sim* s, kb_kernel_time* out, size_t ca
   *n = c;
   return (out && cap < c) ? KB_CAPACITY : KB_OK;
 }
+extern "C" int kb_sim_kernel_breakdown(kb_sim* s, kb_kernel_time* out, size_t cap, size_t* n) {
+  if (!s || !n) return KB_INVALID_ARGUMENT;
+  return route(s, R_FIRST, 0, [&](auto* e) { return eng_kernel_breakdown(e, out, cap, n); });
+}
 // host waits on the device since creation (stream synchronisations and pinned hand-offs); for a
 // group, the largest over its shards
 extern "C" int kb_sim_host_syncs(kb_sim* s, uint64_t* n) {
-  if (s && s->sp) { if (!n) return KB_INVALID_ARGUMENT; *n = s->sp->host_syncs; return KB_OK; }
-  SPG_FIRST([&](kb_sim* t) { return kb_sim_host_syncs(t, n); });
   if (!s || !n) return KB_INVALID_ARGUMENT;
-  if (is_group(s)) {
-    uint64_t m = 0;
-    for (kb_sim* t : s->shards) m = std::max(m, t->host_syncs);
-    *n = m;
-    return KB_OK;
-  }
-  *n = s->host_syncs;
-  return KB_OK;
+  *n = 0;
+  return route(s, R_ALL, 0, [&](auto* e) { *n = std::max<uint64_t>(*n, e->host_syncs); return KB_OK; });
 }
-// OR of the PATH_* bits (kb_common.h) of the kernel variants that did work since creation
-extern "C" int kb_sim_debug_paths(kb_sim* s, uint32_t* mask) {
-  if (s && s->sp) { if (!mask) return KB_INVALID_ARGUMENT; *mask = 0; return KB_OK; }
-  SPG_FIRST([&](kb_sim* t) { return kb_sim_debug_paths(t, mask); });
-  if (!s || !mask) return KB_INVALID_ARGUMENT;
-  if (is_group(s)) {
-    uint32_t m = 0;
-    for (kb_sim* t : s->shards) { uint32_t x = 0; const int rc = kb_sim_debug_paths(t, &x); if (rc) return rc; m |= x; }
-    *mask = m;
-    return KB_OK;
-  }
+// OR of the PATH_* bits (kb_common.h) of the kernel variants that did work since creation (none on the sparse rows)
+static int eng_debug_paths(kb_sim* s, uint32_t* mask) {
   HIPCHK(hipMemcpy(mask, s->d.ctr + C_PATHS, 4, hipMemcpyDeviceToHost));
   return KB_OK;
 }
+static int eng_debug_paths(SpSim*, uint32_t* mask) { *mask = 0; return KB_OK; }
+extern "C" int kb_sim_debug_paths(kb_sim* s, uint32_t* mask) {
+  if (!s || !mask) return KB_INVALID_ARGUMENT;
+  *mask = 0;
+  return route(s, R_ALL, 0, [&](auto* e) {
+    uint32_t x = 0;
+    const int rc = eng_debug_paths(e, &x);
+    *mask |= x;
+    return rc;
+  });
+}
 // development counters (test surface; include/kaboodle_sim.h): the A3 scan's [0..2], the row-shard exchange's bytes
-// [3..4], k_a3_exact's exits [5..9]; an in-process group's are summed over its shards
-extern "C" int kb_sim_debug_counters(kb_sim* s, uint64_t* out, size_t cap) {
-  if (s && s->sp) { if (!out || cap < 3) return KB_INVALID_ARGUMENT; for (size_t k = 0; k < cap && k < 10; ++k) out[k] = 0; return KB_OK; }
-  SPG_FIRST([&](kb_sim* t) { return kb_sim_debug_counters(t, out, cap); });
-  if (!s || !out || cap < 3) return KB_INVALID_ARGUMENT;
-  { const int rc = fold_stats(s); if (rc) return rc; }
+// [3..4], k_a3_exact's exits [5..9]; an in-process group's are summed over its shards; zeros on the sparse rows
+static size_t debug_counters_n(size_t cap) { return cap >= 10 ? 10 : cap >= 5 ? 5 : 3; }
+static int eng_debug_counters(kb_sim* t, uint64_t* out, size_t cap) {
   static_assert(S_A3CHUNKS == S_A3ROWS + 2 && S_A3XWIDE == S_A3X32 + 4, "the A3 counters are read as two blocks");
-  const size_t n = cap >= 10 ? 10 : cap >= 5 ? 5 : 3;
-  for (size_t k = 0; k < n; ++k) out[k] = 0;
-  std::vector<kb_sim*> one{s};
-  for (kb_sim* t : is_group(s) ? s->shards : one) {
-    unsigned long long v[3], x[5];
-    HIPCHK(hipMemcpy(v, t->d.stats + S_A3ROWS, sizeof v, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 3; ++k) out[k] += v[k];
-    if (n >= 5) { out[3] += t->xbytes_cross; out[4] += t->xbytes_all; }   // 0 unsharded
-    if (n < 10) continue;
-    HIPCHK(hipMemcpy(x, t->d.stats + S_A3X32, sizeof x, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 5; ++k) out[5 + k] += x[k];
-  }
+  const size_t n = debug_counters_n(cap);
+  unsigned long long v[3], x[5];
+  { const int rc = fold_stats(t); if (rc) return rc; }
+  HIPCHK(hipMemcpy(v, t->d.stats + S_A3ROWS, sizeof v, hipMemcpyDeviceToHost));
+  for (int k = 0; k < 3; ++k) out[k] += v[k];
+  if (n >= 5) { out[3] += t->xbytes_cross; out[4] += t->xbytes_all; }   // 0 unsharded
+  if (n < 10) return KB_OK;
+  HIPCHK(hipMemcpy(x, t->d.stats + S_A3X32, sizeof x, hipMemcpyDeviceToHost));
+  for (int k = 0; k < 5; ++k) out[5 + k] += x[k];
   return KB_OK;
 }
+static int eng_debug_counters(SpSim*, uint64_t* out, size_t cap) { for (size_t k = 0; k < cap && k < 10; ++k) out[k] = 0; return KB_OK; }
+extern "C" int kb_sim_debug_counters(kb_sim* s, uint64_t* out, size_t cap) {
+  if (!s || !out || cap < 3) return KB_INVALID_ARGUMENT;
+  for (size_t k = 0; k < debug_counters_n(cap); ++k) out[k] = 0;
+  return route(s, R_ALL, 0, [&](auto* e) { return eng_debug_counters(e, out, cap); });
+}
+// the sparse layout's footprint, summed over the shards' rows (the largest row: the max)
+static int eng_footprint(kb_sim*, uint64_t*, size_t) { seterr("not a KB_VARIANT_SPARSE_ROWS handle"); return KB_INVALID_OPERATION; }
 extern "C" int kb_sim_sparse_footprint(kb_sim* s, uint64_t* out, size_t cap) {
   if (!s || !out) return KB_INVALID_ARGUMENT;
-  if (sp_grp(s)) {                                   // summed over the shards' rows (the largest row: the max)
-    if (cap < 6) return KB_INVALID_ARGUMENT;
+  uint64_t acc[6] = {0};
+  const int rc = route(s, R_ALL, 0, [&](auto* e) {
     uint64_t t[6];
-    memset(out, 0, 6 * sizeof(uint64_t));
-    for (kb_sim* sh : s->shards) {
-      const int rc = sp_footprint(sh->sp, t, 6);
-      if (rc) return rc;
-      for (int k = 0; k < 6; ++k) out[k] = k == 3 ? std::max(out[k], t[k]) : out[k] + t[k];
-    }
-    return KB_OK;
-  }
-  if (!s->sp) { seterr("not a KB_VARIANT_SPARSE_ROWS handle"); return KB_INVALID_OPERATION; }
-  return sp_footprint(s->sp, out, cap);
+    const int rc = eng_footprint(e, t, cap);
+    for (int k = 0; !rc && k < 6; ++k) acc[k] = k == 3 ? std::max(acc[k], t[k]) : acc[k] + t[k];
+    return rc;
+  });
+  if (!rc) memcpy(out, acc, sizeof acc);
+  return rc;
 }
+
 
 // ---- the fingerprint checkpoints as stored, and the fold probe (test surface) -------------
 static bool fold_surface_ok(kb_sim* s) {             // dense, and no rank of a kb_sim_create_rank mesh
-  if (!s || s->sp || sp_grp(s)) { seterr("dense handles only"); return false; }
-  if (!is_group(s) && s->xf && !s->in_group) { seterr("not on a kb_sim_create_rank handle"); return false; }
+  if (kind_of(s).sparse) { seterr("dense handles only"); return false; }
+  if (kind_of(s).rank) { seterr("not on a kb_sim_create_rank handle"); return false; }
   return true;
 }
 extern "C" int kb_sim_dump_checkpoints(kb_sim* s, uint32_t node, uint32_t* seg, uint64_t* stale, uint32_t* dirty,
@@ -2508,8 +2141,8 @@ extern "C" int kb_sim_dump_checkpoints(kb_sim* s, uint32_t node, uint32_t* seg, 
   if (!s) return KB_INVALID_ARGUMENT;
   if (!fold_surface_ok(s)) return KB_INVALID_OPERATION;
   if (chk(s, node) || !seg || !stale || !dirty || !fp_cached) return KB_INVALID_ARGUMENT;
-  GROUP_OWNER(node, [&](kb_sim* t) { return kb_sim_dump_checkpoints(t, node, seg, stale, dirty, fp_cached); });
-  if (chk_row(s, node)) return KB_INVALID_ARGUMENT;
+  if (is_group(s)) s = owner(s, node);
+  if (ctl_chk_row(s, node)) return KB_INVALID_ARGUMENT;
   (void)hipSetDevice(s->device);
   uint8_t dy = 0;
   HIPCHK(hipMemcpy(seg, s->d.segp + (size_t)node * NSEG, 8ull * NSEG, hipMemcpyDeviceToHost));

@@ -168,7 +168,7 @@ static void sp_scan(SpSim* S, uint32_t n, int narr, const uint32_t* const* in, u
 }
 
 // per-id segment CRCs and uniformity (identity changes), on the host tables
-static int sp_upload_segments(SpSim* S) {
+static int upload_segments(SpSim* S) {
   const uint32_t C = S->C;
   std::vector<uint32_t> cseg(C), segmul(C), seglen(C);
   bool uniform = true;
@@ -272,7 +272,7 @@ static int sp_create(const kb_config* cfg, int rank, int world, Xfer* xf, SpSim*
   if (e != hipSuccess) { seterr(std::string("sparse engine: device allocation failed: ") + hipGetErrorString(e)); sp_destroy(S); return KB_CAPACITY; }
   if (hipStreamCreateWithFlags(&S->st, hipStreamNonBlocking) != hipSuccess) { sp_destroy(S); seterr("stream"); return KB_IO_ERROR; }
   if (const char* pv = getenv("KB_PROF")) S->prof_level = atoi(pv);
-  { const int rc = sp_upload_segments(S); if (rc) { sp_destroy(S); return rc; } }
+  { const int rc = upload_segments(S); if (rc) { sp_destroy(S); return rc; } }
   // the base (the initial members of a converged start) with its prefix counts and prefix folds, and Z^k
   {
     const uint32_t nb = d.nb;
@@ -305,7 +305,7 @@ static int sp_create(const kb_config* cfg, int rank, int world, Xfer* xf, SpSim*
   return KB_OK;
 }
 
-static int sp_read_row(SpSim* S, uint32_t node, std::vector<uint8_t>& rw);
+static int read_row(SpSim* S, uint32_t node, std::vector<uint8_t>& rw);
 static int sp_xfail(SpSim* S) { seterr(S->xf->error()); return KB_IO_ERROR; }
 // one all-to-all-v pair (records + ids, or two lists) as one group; an opened group is always closed
 static int sp_a2a2(SpSim* S, const void* s1, const size_t* sc1, const size_t* sd1, void* r1, const size_t* rc1, const size_t* rd1,
@@ -389,7 +389,7 @@ static int sp_apply_events(SpSim* S, int32_t r) {
       if (snap_after) {
         std::vector<uint8_t> rw;
         HIPCHK(sp_sync(S));
-        const int rc = sp_read_row(S, ev.node, rw);
+        const int rc = read_row(S, ev.node, rw);
         if (rc) return rc;
         for (size_t q = 0; q < S->watch_node.size(); ++q)
           if (S->watch_node[q] == ev.node) for (uint32_t j = 0; j < C; ++j) S->watch_snap[q][j] = rw[j] != 0;
@@ -414,7 +414,7 @@ static int sp_apply_events(SpSim* S, int32_t r) {
       k0 = k + 1;
       std::vector<uint8_t> rw;
       HIPCHK(sp_sync(S));
-      const int rc = sp_read_row(S, ev.node, rw);
+      const int rc = read_row(S, ev.node, rw);
       if (rc) return rc;
       for (uint32_t j = 0; j < C; ++j) S->watch_snap[kt][j] = rw[j] != 0;
     }
@@ -757,7 +757,7 @@ static int sp_entries(SpSim* S, uint32_t node, std::vector<uint32_t>& e, uint8_t
   if (n) HIPCHK(hipMemcpy(e.data(), S->d.ent + (size_t)node * S->d.ESTR, 4ull * n, hipMemcpyDeviceToHost));
   return KB_OK;
 }
-static int sp_read_row(SpSim* S, uint32_t node, std::vector<uint8_t>& rw) {   // canonical bytes (0 = not a member)
+static int read_row(SpSim* S, uint32_t node, std::vector<uint8_t>& rw) {   // canonical bytes (0 = not a member)
   std::vector<uint32_t> e;
   uint8_t based = 0;
   const int rc = sp_entries(S, node, e, &based);
@@ -771,143 +771,20 @@ static int sp_read_row(SpSim* S, uint32_t node, std::vector<uint8_t>& rw) {   //
   }
   return KB_OK;
 }
-static int sp_api_running(SpSim* S, uint32_t node, int* run) {
-  for (size_t k = S->events.size(); k-- > 0;) {
-    if (S->events[k].node == node) { *run = S->events[k].kind != EV_STOP; return KB_OK; }
-    if (S->events[k].kind == EV_RESTART && S->events[k].src == node) { *run = 0; return KB_OK; }
-  }
-  uint8_t a = 0;
-  HIPCHK(hipMemcpy(&a, S->d.alive + node, 1, hipMemcpyDeviceToHost));
-  *run = a;
-  return KB_OK;
-}
-static int sp_ever_bound(SpSim* S, uint32_t node, int* ever) {
-  for (const Event& e : S->events) if (e.node == node && e.kind != EV_STOP) { *ever = 1; return KB_OK; }
-  int32_t sr = 0;
-  HIPCHK(hipMemcpy(&sr, S->d.start_round + node, 4, hipMemcpyDeviceToHost));
-  *ever = sr != NONE_ROUND;
-  return KB_OK;
-}
-static int sp_start_node(SpSim* S, uint32_t node) {
-  int run = 0, ever = 0;
-  { int rc = sp_api_running(S, node, &run); if (!rc) rc = sp_ever_bound(S, node, &ever); if (rc) return rc; }
-  if (!run && ever) { seterr("a stopped instance restarts at a fresh address (kb_sim_restart_node)"); return KB_INVALID_OPERATION; }
-  S->events.push_back(Event{node, EV_START, node, 0});
-  return KB_OK;
-}
-static int sp_stop_node(SpSim* S, uint32_t node) { S->events.push_back(Event{node, EV_STOP, node, 0}); return KB_OK; }
-static int sp_restart_node(SpSim* S, uint32_t node, uint32_t* new_node) {
-  if (S->h_moved[node]) { seterr("the instance bound here restarted at a fresh address"); return KB_INVALID_OPERATION; }
-  int run = 0, ever = 0;
-  { int rc = sp_api_running(S, node, &run); if (!rc) rc = sp_ever_bound(S, node, &ever); if (rc) return rc; }
-  if (run) { *new_node = node; return KB_OK; }
-  if (!ever) { *new_node = node; S->events.push_back(Event{node, EV_START, node, 0}); return KB_OK; }
-  uint32_t nf = 0;
-  HIPCHK(hipMemcpy(&nf, S->d.ctr + C_NEXTFREE, 4, hipMemcpyDeviceToHost));
-  for (; nf < S->C; ++nf) {                          // the next fresh id: never bound, no identity set
-    int ev = 0;
-    const int rc = sp_ever_bound(S, nf, &ev);
-    if (rc) return rc;
-    if (!ev && !S->h_idset[nf]) break;
-  }
-  if (nf >= S->C) { seterr("no fresh address left for the restart (capacity)"); return KB_CAPACITY; }
-  const uint32_t to = nf;
-  const int pl = S->h_pendlen[node];
-  const uint8_t* src = pl >= 0 ? &S->h_pend[(size_t)node * MAXID] : &S->h_ident[(size_t)node * MAXID];
-  const uint32_t len = pl >= 0 ? (uint32_t)pl : S->h_idlen[node];
-  memmove(&S->h_ident[(size_t)to * MAXID], src, len);
-  S->h_idlen[to] = (uint8_t)len;
-  S->h_pendlen[node] = -1; S->h_pendlen[to] = -1;
-  { const int rc = sp_upload_segments(S); if (rc) return rc; }
-  const uint32_t nn = to + 1;
-  HIPCHK(hipMemcpy(S->d.ctr + C_NEXTFREE, &nn, 4, hipMemcpyHostToDevice));
-  S->events.push_back(Event{to, EV_RESTART, node, 0});
-  S->h_moved[node] = 1;
-  *new_node = to;
-  return KB_OK;
-}
-static int sp_is_running(SpSim* S, uint32_t node, int* running) {
-  uint8_t a = 0;
-  HIPCHK(hipMemcpy(&a, S->d.alive + node, 1, hipMemcpyDeviceToHost));
-  *running = a;
-  return KB_OK;
-}
-static int sp_ping_addrs(SpSim* S, uint32_t node, const uint32_t* peers, size_t n) {
-  for (size_t k = 0; k < n; ++k) if (peers[k] >= S->C) return KB_INVALID_ARGUMENT;
-  int run = 0;
-  { const int rc = sp_is_running(S, node, &run); if (rc) return rc; }
-  if (!run) { seterr("Cannot ping while we are not started"); return KB_INVALID_OPERATION; }
-  if (node < S->lo || node >= S->hi) return KB_OK;   // queued by the shard holding the row
-  uint32_t qn = 0;
-  HIPCHK(hipMemcpy(&qn, S->d.paq_n + node, 4, hipMemcpyDeviceToHost));
-  std::vector<uint32_t> q(PAQ);
-  HIPCHK(hipMemcpy(q.data(), S->d.paq + (size_t)node * PAQ, 4 * PAQ, hipMemcpyDeviceToHost));
-  std::vector<uint8_t> rw;
-  { const int rc = sp_read_row(S, node, rw); if (rc) return rc; }
-  for (size_t k = 0; k < n; ++k) {
-    if (rw[peers[k]]) continue;                      // already known: skipped (src/lib.rs:277-282)
-    if (qn == PAQ) { seterr("ping_addrs queue full"); return KB_CAPACITY; }
-    q[qn++] = peers[k];
-  }
-  HIPCHK(hipMemcpy(S->d.paq + (size_t)node * PAQ, q.data(), 4 * PAQ, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(S->d.paq_n + node, &qn, 4, hipMemcpyHostToDevice));
-  return KB_OK;
-}
-static int sp_set_identity(SpSim* S, uint32_t node, const uint8_t* identity, size_t len) {
-  if (S->h_moved[node]) { seterr("the instance bound here restarted at a fresh address"); return KB_INVALID_OPERATION; }
-  int run = 0, ever = 0;
-  { int rc = sp_api_running(S, node, &run); if (!rc) rc = sp_ever_bound(S, node, &ever); if (rc) return rc; }
-  if (run) { seterr("Cannot change identity while the mesh is running; call .stop first"); return KB_INVALID_OPERATION; }
-  if (len != S->cfg.id_len && S->C > 200) { seterr("non-uniform identity length needs capacity <= 200"); return KB_INVALID_ARGUMENT; }
-  if (ever) {
-    memcpy(&S->h_pend[(size_t)node * MAXID], identity, len);
-    S->h_pendlen[node] = (int16_t)len;
-    return KB_OK;
-  }
-  memcpy(&S->h_ident[(size_t)node * MAXID], identity, len);
-  S->h_idlen[node] = (uint8_t)len;
-  S->h_idset[node] = 1;                            // no longer a fresh id for churn joins and restarts
-  { const uint8_t one = 1; HIPCHK(hipMemcpy(S->d.idset + node, &one, 1, hipMemcpyHostToDevice)); }
-  { const int rc = sp_upload_segments(S); if (rc) return rc; }
+// ---- the control plane's hooks (kb_ctl.h) ---------------------------------------------------------------
+static int mark_all_dirty(SpSim* S) {
   k_sp_mark_dirty<<<(S->R + 255) / 256, 256, 0, S->st>>>(S->d);
   HIPCHK(hipStreamSynchronize(S->st));
   return KB_OK;
 }
-static int sp_identity(SpSim* S, uint32_t node, uint8_t* buf, size_t cap, size_t* len) {
-  *len = S->h_idlen[node];
-  if (!buf) return KB_OK;
-  if (cap < *len) return KB_CAPACITY;
-  memcpy(buf, &S->h_ident[(size_t)node * MAXID], *len);
+static int export_alloc(SpSim* S) {
+  S->d.xrec_cap = 1u << 16; S->d.xids_cap = 1u << 22;
+  HIPCHK(sp_alloc(S, &S->d.xrec, S->d.xrec_cap)); HIPCHK(sp_alloc(S, &S->d.xids, S->d.xids_cap));
   return KB_OK;
 }
-static int sp_probe_responses(SpSim* S, kb_probe_response* out, size_t cap, size_t* n) {
-  *n = S->presp.size();
-  if (!out) return KB_OK;
-  if (cap < S->presp.size()) return KB_CAPACITY;
-  if (!S->presp.empty()) memcpy(out, S->presp.data(), S->presp.size() * sizeof(kb_probe_response));
-  S->presp.clear();
-  return KB_OK;
-}
-static int sp_broadcasts(SpSim* S, kb_broadcast* out, size_t cap, size_t* n) {
-  std::vector<BCast> j(S->nj), f(S->nf);
-  if (S->nj) HIPCHK(hipMemcpy(j.data(), S->bjoin, sizeof(BCast) * S->nj, hipMemcpyDeviceToHost));
-  if (S->nf) HIPCHK(hipMemcpy(f.data(), S->bfail, sizeof(BCast) * S->nf, hipMemcpyDeviceToHost));
-  size_t c = 0, a = 0, b = 0;
-  while (a < j.size() || b < f.size()) {
-    const bool tj = b == f.size() || (a < j.size() && j[a].sender <= f[b].sender);
-    if (out && c < cap) {
-      kb_broadcast& o = out[c];
-      memset(&o, 0, sizeof o);
-      if (tj) { o.kind = KB_WIRE_JOIN; o.sender = j[a].sender; o.peer = j[a].peer; }
-      else { o.kind = KB_WIRE_FAILED; o.sender = f[b].sender; o.peer = f[b].peer; }
-    }
-    if (tj) a++; else b++;
-    c++;
-  }
-  *n = c;
-  return (out && cap < c) ? KB_CAPACITY : KB_OK;
-}
-static int sp_fingerprint(SpSim* S, uint32_t node, uint32_t* fp) {
+static void window_stale(SpSim*) {}                  // no captured receive window
+static int lat_column(SpSim*, uint32_t, std::vector<uint16_t>&) { return KB_OK; }   // no latency table
+static int row_fp(SpSim* S, uint32_t node, uint32_t* fp) {
   { const int rc = sp_chk_row(S, node); if (rc) return rc; }
   k_sp_fp_one<<<1, 64, 0, S->st>>>(S->d, node);
   HIPCHK(hipMemcpyAsync(fp, S->d.fp + node, 4, hipMemcpyDeviceToHost, S->st));
@@ -915,7 +792,7 @@ static int sp_fingerprint(SpSim* S, uint32_t node, uint32_t* fp) {
   return KB_OK;
 }
 // all ids; 0 for non-running ids and for rows held by other shards
-static int sp_fingerprints(SpSim* S, uint32_t* fps) {
+static int eng_fingerprints(SpSim* S, uint32_t* fps) {
   k_sp_fp_all<<<(S->R + 255) / 256, 256, 0, S->st>>>(S->d);
   std::vector<uint8_t> al(S->C);
   memset(fps, 0, 4ull * S->C);
@@ -925,59 +802,27 @@ static int sp_fingerprints(SpSim* S, uint32_t* fps) {
   for (uint32_t i = 0; i < S->C; ++i) if (!al[i]) fps[i] = 0;
   return KB_OK;
 }
-static int sp_true_fingerprint(SpSim* S, uint32_t* fp) {
+static int eng_true_fingerprint(SpSim* S, uint32_t* fp) {
   k_sp_truefp_part<<<SP_TFP / 256, 256, 0, S->st>>>(S->d, S->tfpart);
   k_sp_truefp_fin<<<1, 64, 0, S->st>>>(S->d, (const uint2*)S->tfpart, S->tfp);
   HIPCHK(hipMemcpyAsync(fp, S->tfp, 4, hipMemcpyDeviceToHost, S->st));
   HIPCHK(hipStreamSynchronize(S->st));
   return KB_OK;
 }
-static int sp_peer_states(SpSim* S, uint32_t node, kb_peer_state* out, size_t cap, size_t* n) {
-  { const int rc = sp_chk_row(S, node); if (rc) return rc; }
-  std::vector<uint8_t> rw;
-  { const int rc = sp_read_row(S, node, rw); if (rc) return rc; }
-  Susp sl[SLOTS];
-  HIPCHK(hipMemcpy(sl, S->d.susp + (size_t)node * SLOTS, sizeof sl, hipMemcpyDeviceToHost));
-  const int32_t E = epoch_base(S->round > 0 ? S->round - 1 : 0);
-  size_t c = 0;
-  for (uint32_t j = 0; j < S->C; ++j) {
-    if (!rw[j]) continue;
-    if (out && c < cap) {
-      kb_peer_state& o = out[c];
-      memset(&o, 0, sizeof o);
-      o.peer = j;
-      o.identity_len = S->h_idlen[j];
-      memcpy(o.identity, &S->h_ident[(size_t)j * MAXID], S->h_idlen[j]);
-      o.latency_ms = KB_LATENCY_NONE;
-      if (rw[j] == ST_SUSPECT) {
-        const Susp* q = nullptr;
-        for (auto& x : sl) if (x.kind && x.peer == j) q = &x;
-        o.state = q && q->kind == SK_WFIP ? KB_STATE_WAITING_FOR_INDIRECT_PING : KB_STATE_WAITING_FOR_PING;
-        o.since = q ? q->since : 0;
-      } else {
-        o.state = KB_STATE_KNOWN;
-        o.since = rw[j] == ST_ANCIENT ? INT32_MIN : (int32_t)rw[j] + E - EOFF;
-      }
-    }
-    c++;
-  }
-  *n = c;
-  return (out && cap < c) ? KB_CAPACITY : KB_OK;
-}
-static int sp_watch(SpSim* S, uint32_t node) {
+static int eng_watch(SpSim* S, uint32_t node) {
   { const int rc = sp_chk_row(S, node); if (rc) return rc; }
   for (uint32_t w : S->watch_node) if (w == node) return KB_OK;
   S->watch_node.push_back(node); S->watch_fp.push_back(0); S->watch_snap.emplace_back(S->C, 0);   // attached empty
   return KB_OK;
 }
-static int sp_events(SpSim* S, uint32_t node, uint32_t* discovered, size_t cap_d, size_t* n_d, uint32_t* departed, size_t cap_p,
+static int eng_events(SpSim* S, uint32_t node, uint32_t* discovered, size_t cap_d, size_t* n_d, uint32_t* departed, size_t cap_p,
                      size_t* n_p, uint32_t* fp, int* fp_changed) {
   size_t k = 0;
   while (k < S->watch_node.size() && S->watch_node[k] != node) ++k;
   if (k == S->watch_node.size()) { seterr("node is not watched (kb_sim_watch)"); return KB_INVALID_OPERATION; }
   std::vector<uint8_t> rw;
-  { const int rc = sp_read_row(S, node, rw); if (rc) return rc; }
-  { const int rc = sp_fingerprint(S, node, fp); if (rc) return rc; }
+  { const int rc = read_row(S, node, rw); if (rc) return rc; }
+  { const int rc = row_fp(S, node, fp); if (rc) return rc; }
   std::vector<uint8_t>& snap = S->watch_snap[k];
   size_t a = 0, rm = 0, known = 0;
   for (uint32_t j = 0; j < S->C; ++j) {
@@ -1001,104 +846,15 @@ static int sp_events(SpSim* S, uint32_t node, uint32_t* discovered, size_t cap_d
   if (*fp_changed) S->watch_fp[k] = *fp;
   return KB_OK;
 }
-static int sp_fold_stats(SpSim* S) {
+static int fold_stats(SpSim* S) {
   (void)hipSetDevice(S->device);
   k_sp_stats_fold<<<NSTAT, 256, 0, S->st>>>(S->d);
   HIPCHK(hipStreamSynchronize(S->st));
   return KB_OK;
 }
-// this shard's counters (ranks of kb_sim_create_rank: summed over the mesh, a collective)
-static int sp_read_stats(SpSim* S, unsigned long long* st) {
-  { const int rc = sp_fold_stats(S); if (rc) return rc; }
-  if (S->xf && !S->in_group) {
-    HIPCHK(hipMemcpyAsync(S->xstats, S->d.stats, 8ull * NSTAT, hipMemcpyDeviceToDevice, S->st));
-    if (!S->xf->allreduce_sum_u64(S->xstats, NSTAT, S->st)) return sp_xfail(S);
-    HIPCHK(hipMemcpyAsync(st, S->xstats, 8ull * NSTAT, hipMemcpyDeviceToHost, S->st));
-    HIPCHK(hipStreamSynchronize(S->st));
-    return KB_OK;
-  }
-  HIPCHK(hipMemcpy(st, S->d.stats, 8ull * NSTAT, hipMemcpyDeviceToHost));
-  return KB_OK;
-}
-// kb_stats from the mesh's counters `st` and this shard's replicated facts
-static int sp_stats_fill(SpSim* S, const unsigned long long* st, kb_stats* out) {
-  uint32_t ctr[NCTR];
-  HIPCHK(hipMemcpy(ctr, S->d.ctr, sizeof ctr, hipMemcpyDeviceToHost));
-  std::vector<uint8_t> al(S->C);
-  HIPCHK(hipMemcpy(al.data(), S->d.alive, S->C, hipMemcpyDeviceToHost));
-  memset(out, 0, sizeof *out);
-  out->round = S->round;
-  uint32_t a = 0;
-  for (uint8_t x : al) a += x;
-  out->alive = a;
-  out->agree = ctr[C_LASTAGREE];
-  out->first_converged_round = (int32_t)ctr[C_FIRSTCONV];
-  out->last_converged_round = (int32_t)ctr[C_LASTCONV];
-  out->next_free_id = ctr[C_NEXTFREE];
-  out->sent_ping = st[S_PING]; out->sent_ping_req = st[S_PINGREQ]; out->sent_ack = st[S_ACK];
-  out->sent_known_peers = st[S_KP]; out->sent_kpr = st[S_KPR];
-  out->bcast_join = S->bj_total; out->bcast_failed = S->bf_total;
-  out->drop_dead = st[S_DEAD]; out->drop_loss = st[S_LOSS]; out->drop_window = st[S_WINDOW];
-  out->drop_oversize = st[S_OVERSIZE]; out->drop_partition = st[S_PART]; out->drop_bcast = st[S_BDROP];
-  out->removed_timeout = st[S_RMTIMEOUT]; out->removed_failed = st[S_RMFAILED]; out->join_responses = st[S_JRESP];
-  out->curious_overflow = st[S_CUROVF]; out->churn_leaves = st[S_CLEAVE]; out->churn_joins = st[S_CJOIN];
-  out->sent_kp_ids = st[S_KPIDS];
-  out->alive_rounds = st[S_ALIVER];
-  out->probe_responses = st[S_PROBERESP];
-  out->exported = st[S_EXPORT];
-  return KB_OK;
-}
-static int sp_stats_out(SpSim* S, kb_stats* out) {
-  unsigned long long st[NSTAT];
-  { const int rc = sp_read_stats(S, st); if (rc) return rc; }
-  return sp_stats_fill(S, st, out);
-}
-// per id: alive, n, last_bcast, start_round; n and last_bcast only for the rows this handle holds
-static int sp_dump_scalars(SpSim* S, int32_t* out) {
-  const uint32_t C = S->C, R = S->R;
-  std::vector<uint8_t> al(C);
-  std::vector<uint32_t> n(R);
-  std::vector<int32_t> lb(R), sr(C);
-  HIPCHK(hipMemcpy(al.data(), S->d.alive, C, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(n.data(), SL(S, S->d.n), 4ull * R, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(lb.data(), SL(S, S->d.last_bcast), 4ull * R, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(sr.data(), S->d.start_round, 4ull * C, hipMemcpyDeviceToHost));
-  for (uint32_t i = 0; i < C; ++i) {
-    const bool loc = i >= S->lo && i < S->hi;
-    out[4 * i] = al[i]; out[4 * i + 1] = loc ? (int32_t)n[i - S->lo] : 0;
-    out[4 * i + 2] = loc ? lb[i - S->lo] : 0; out[4 * i + 3] = sr[i];
-  }
-  return KB_OK;
-}
-static int sp_dump_suspects(SpSim* S, uint32_t node, int32_t* out, size_t cap, size_t* n) {
-  { const int rc = sp_chk_row(S, node); if (rc) return rc; }
-  Susp sl[SLOTS];
-  HIPCHK(hipMemcpy(sl, S->d.susp + (size_t)node * SLOTS, sizeof sl, hipMemcpyDeviceToHost));
-  std::vector<std::array<int32_t, 3>> v;
-  for (auto& x : sl) if (x.kind) v.push_back({(int32_t)x.peer, x.kind, x.since});
-  std::sort(v.begin(), v.end());
-  *n = v.size();
-  if (out) { if (cap < 3 * v.size()) return KB_CAPACITY; for (size_t k = 0; k < v.size(); ++k) memcpy(out + 3 * k, v[k].data(), 12); }
-  return KB_OK;
-}
-static int sp_dump_curious(SpSim* S, uint32_t node, int32_t* out, size_t cap, size_t* n) {
-  { const int rc = sp_chk_row(S, node); if (rc) return rc; }
-  Cur cu[CSLOTS];
-  HIPCHK(hipMemcpy(cu, S->d.cur + (size_t)node * CSLOTS, sizeof cu, hipMemcpyDeviceToHost));
-  std::vector<std::array<int32_t, 6>> v;
-  for (auto& x : cu) if (x.used) {
-    std::array<int32_t, 6> e{(int32_t)x.peer, (int32_t)x.nobs, -1, -1, -1, -1};
-    for (uint32_t q = 0; q < x.nobs && q < NOBS; ++q) e[2 + q] = (int32_t)x.obs[q];
-    v.push_back(e);
-  }
-  std::sort(v.begin(), v.end(), [](const std::array<int32_t, 6>& a, const std::array<int32_t, 6>& b) { return a[0] < b[0]; });
-  *n = v.size();
-  if (out) { if (cap < 6 * v.size()) return KB_CAPACITY; for (size_t k = 0; k < v.size(); ++k) memcpy(out + 6 * k, v[k].data(), 24); }
-  return KB_OK;
-}
 // kb_sim_kernel_time kinds: the whole round; the tick (KB_KT_ROWPASS's place: the per-row pass of the round);
 // the in-order handlers (KB_KT_PROC)
-static int sp_kernel_time(SpSim* S, int kind, double* ms, uint64_t* launches) {
+static int eng_kernel_time(SpSim* S, int kind, double* ms, uint64_t* launches) {
   (void)hipStreamSynchronize(S->st);
   sp_prof_resolve(S);
   const int k = kind == KB_KT_ROUND ? SPK_N : kind == KB_KT_ROWPASS ? SPK_TICK : kind == KB_KT_PROC ? SPK_HANDLE : -1;
@@ -1107,14 +863,14 @@ static int sp_kernel_time(SpSim* S, int kind, double* ms, uint64_t* launches) {
   else { *ms = S->k_ms[k]; *launches = S->k_n[k]; }
   return KB_OK;
 }
-static int sp_reset_kernel_time(SpSim* S) {
+static int eng_reset_kernel_time(SpSim* S) {
   (void)hipStreamSynchronize(S->st);
   sp_prof_resolve(S);
   S->round_ms = 0; S->round_n = 0;
   memset(S->k_ms, 0, sizeof S->k_ms); memset(S->k_n, 0, sizeof S->k_n);
   return KB_OK;
 }
-static int sp_kernel_breakdown(SpSim* S, kb_kernel_time* out, size_t cap, size_t* n) {
+static int eng_kernel_breakdown(SpSim* S, kb_kernel_time* out, size_t cap, size_t* n) {
   (void)hipStreamSynchronize(S->st);
   sp_prof_resolve(S);
   size_t c = 0;
@@ -1131,59 +887,9 @@ static int sp_kernel_breakdown(SpSim* S, kb_kernel_time* out, size_t cap, size_t
   *n = c;
   return (out && cap < c) ? KB_CAPACITY : KB_OK;
 }
-// external peers: the dense engine's rules (kb_sim.hip kb_sim_set_external / inject / exported)
-static int sp_set_external(SpSim* S, uint32_t node) {
-  if (S->h_ext.empty()) S->h_ext.assign(S->C, 0);
-  if (S->h_ext[node]) return KB_OK;
-  int ever = 0;
-  { const int rc = sp_ever_bound(S, node, &ever); if (rc) return rc; }
-  if (ever) { seterr("an external peer takes an address no instance has bound"); return KB_INVALID_OPERATION; }
-  S->h_ext[node] = 1; S->n_ext++; S->h_idset[node] = 1;
-  const uint8_t o = 1;
-  HIPCHK(hipMemcpy(S->d.ext + node, &o, 1, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(S->d.idset + node, &o, 1, hipMemcpyHostToDevice));
-  if (!S->d.xrec) {
-    S->d.xrec_cap = 1u << 16; S->d.xids_cap = 1u << 22;
-    HIPCHK(sp_alloc(S, &S->d.xrec, S->d.xrec_cap)); HIPCHK(sp_alloc(S, &S->d.xids, S->d.xids_cap));
-  }
-  return KB_OK;
-}
-static int sp_inject(SpSim* S, const kb_unicast* m, const uint32_t* ids) {
-  if (!m || m->sender >= S->C || m->dest >= S->C || (m->kind > K_KPR && m->kind != KB_WIRE_JOIN) || (m->pay_len && !ids))
-    return KB_INVALID_ARGUMENT;
-  if (S->h_ext.empty() || !S->h_ext[m->sender]) { seterr("kb_sim_inject: the sender is not an external peer"); return KB_INVALID_OPERATION; }
-  if (m->kind == KB_WIRE_JOIN) {                       // a Join broadcast: the next round's Join list
-    if (std::find(S->inj_join.begin(), S->inj_join.end(), m->sender) != S->inj_join.end()) {
-      seterr("kb_sim_inject: one Join per external peer per round"); return KB_CAPACITY;
-    }
-    S->inj_join.push_back(m->sender);
-    return KB_OK;
-  }
-  if ((m->kind == K_PINGREQ || m->kind == K_ACK) && m->a >= S->C) return KB_INVALID_ARGUMENT;
-  for (uint32_t k = 0; k < m->pay_len; ++k) if (ids[k] >= S->C) return KB_INVALID_ARGUMENT;
-  uint32_t per = 0, rel = 0;
-  for (const XRec& x : S->inj) if (x.sender == m->sender) { per++; if (x.kind == K_KP) rel += x.pay_len; }
-  if (per >= (uint32_t)TICK_MAX) { seterr("kb_sim_inject: 33 records per external peer per round"); return KB_CAPACITY; }
-  XRec x{0, 0, m->sender, m->dest, 0, m->kind, m->kind == K_KP ? 0u : m->a, m->fp, m->n, (uint32_t)S->inj_ids.size(),
-         m->kind == K_KP ? m->pay_len : 0u, rel};
-  if (m->kind == K_KP) S->inj_ids.insert(S->inj_ids.end(), ids, ids + m->pay_len);
-  S->inj.push_back(x);
-  return KB_OK;
-}
-static int sp_exported(SpSim* S, kb_unicast* out, size_t cap, size_t* n, uint32_t* ids, size_t cap_ids, size_t* n_ids) {
-  *n = S->xq.size(); *n_ids = S->xq_ids.size();
-  if (!out && !ids) return KB_OK;
-  if (cap < S->xq.size() || (!S->xq_ids.empty() && (!ids || cap_ids < S->xq_ids.size()))) { seterr("export buffer too small"); return KB_CAPACITY; }
-  if (!S->xq.empty()) memcpy(out, S->xq.data(), S->xq.size() * sizeof(kb_unicast));
-  for (const kb_unicast& u : S->xq)                    // a KnownPeers map has no order: ascending ids
-    std::sort(S->xq_ids.begin() + u.pay_off, S->xq_ids.begin() + u.pay_off + u.pay_len);
-  if (!S->xq_ids.empty()) memcpy(ids, S->xq_ids.data(), 4 * S->xq_ids.size());
-  S->xq.clear(); S->xq_ids.clear();
-  return KB_OK;
-}
 // the sparse layout's footprint (test surface): [rows based, exceptions, explicit stamps, entries of the
 // largest row, bytes (4 per entry), rows], the oracle's kbo_sparse_footprint in this layout
-static int sp_footprint(SpSim* S, uint64_t* out, size_t cap) {   // over the rows this handle holds
+static int eng_footprint(SpSim* S, uint64_t* out, size_t cap) {   // over the rows this handle holds
   if (cap < 6) return KB_INVALID_ARGUMENT;
   const uint32_t lo = S->lo, hi = S->hi, R = S->R;
   std::vector<uint32_t> ne(R);
