@@ -14,6 +14,7 @@
 #include "kaboodle_census.h"
 #include "kaboodle_reciprocity.h"
 #include "kaboodle_classes.h"
+#include "kaboodle_latency.h"
 
 namespace kb {
 
@@ -90,6 +91,27 @@ class Mesh {
                             arrays ? r.size.data() : nullptr, r.rep.size()),
           "kb_sim_fp_classes");
     r.classes.resize(n);
+    return r;
+  }
+
+  // the latency census (kaboodle_latency.h; HIP library only, dense handles with track_latency): the ping-latency
+  // table read mesh-wide.  Per id: the observers holding a first-hand latency of it, their sum, min and max; per row:
+  // its measured entries and their sum.  arrays = false asks for the summary alone.
+  struct LatencyCensus {
+    kb_lat_census summary;
+    std::vector<uint32_t> measured_by, min_ms, max_ms, measured;
+    std::vector<uint64_t> sum_ms, row_sum_ms;
+  };
+  LatencyCensus latency_census(bool arrays = true) const {
+    LatencyCensus r;
+    if (arrays) {
+      r.measured_by.resize(capacity_); r.min_ms.resize(capacity_); r.max_ms.resize(capacity_); r.sum_ms.resize(capacity_);
+      r.measured.resize(capacity_); r.row_sum_ms.resize(capacity_);
+    }
+    check(kb_sim_latency_census(h_, &r.summary, arrays ? r.measured_by.data() : nullptr, arrays ? r.sum_ms.data() : nullptr,
+                                arrays ? r.min_ms.data() : nullptr, arrays ? r.max_ms.data() : nullptr, r.measured_by.size(),
+                                arrays ? r.measured.data() : nullptr, arrays ? r.row_sum_ms.data() : nullptr, r.measured.size()),
+          "kb_sim_latency_census");
     return r;
   }
 

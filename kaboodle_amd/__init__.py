@@ -101,6 +101,20 @@ class Mesh(Sim):
         rep) and per id the representative and size of its class.  Rank shards raise KbError: a class spans ranks."""
         return super().fp_classes(top, arrays)
 
+    def latency_census(self, arrays: bool = True):
+        """The ping-latency table mesh-wide (include/kaboodle_latency.h) in one pass on the GPU: per
+        peer how many observers measured it first-hand and the sum, minimum and maximum of their latencies, per row
+        how many of its entries are measured, a log2 histogram of all measured values and the table's orphan
+        count.  Returns a `latency.LatencyCensus`.  Needs track_latency; sparse rows and rank shards raise KbError."""
+        return super().latency_census(arrays)
+
+
+def latency_census_of(lat, member, running, arrays: bool = True, device: int = 0):
+    """The latency census's GPU kernel over host arrays (kb_latency_census_of, a test surface): `lat` peer-major
+    [n_ids][n_rows] uint16, `member` [n_rows][n_ids], `running` [n_rows]; a `latency.LatencyCensus`."""
+    from ._ffi import latency_census_of as _of
+    return _of(lib(), lat, member, running, arrays, device)
+
 
 def fp_classes_of(fps, running, true_fp: int, top: int = 16, arrays: bool = True, device: int = 0):
     """The class census's GPU kernels over host arrays (kb_fp_classes_of, a test surface): `classes.FpClasses`."""

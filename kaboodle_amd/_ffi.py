@@ -124,6 +124,23 @@ _FPC_OUT = [C.POINTER(KbFpClasses), C.POINTER(KbFpClass), C.c_size_t, C.POINTER(
             C.POINTER(C.c_uint32), C.c_size_t]
 
 
+class KbLatCensus(C.Structure):
+    """kb_lat_census (include/kaboodle_latency.h)."""
+    _fields_ = [("round", C.c_int32), ("observers", C.c_uint32), ("measured", C.c_uint64), ("sum_ms", C.c_uint64),
+                ("min_ms", C.c_uint32), ("max_ms", C.c_uint32), ("max_peer", C.c_uint32), ("measured_ids", C.c_uint32),
+                ("hist", C.c_uint64 * 17), ("orphans", C.c_uint64), ("reserved", C.c_uint64 * 4)]
+
+    def as_dict(self) -> dict:
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n not in ("reserved", "hist")}
+        d["hist"] = [int(x) for x in self.hist]
+        return {k: d[k] for k in ("round", "observers", "measured", "sum_ms", "min_ms", "max_ms", "max_peer",
+                                  "measured_ids", "hist", "orphans")}
+
+
+_LATC_OUT = [C.POINTER(KbLatCensus), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+             C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t]
+
+
 KB_FOLD_TICK, KB_FOLD_FP_ALL, KB_FOLD_FP_ONE, KB_FOLD_THREAD = 0, 1, 2, 3   # kb_fold_probe.path
 NSEG = 64                        # fingerprint checkpoints per row
 
@@ -288,6 +305,12 @@ _OPTIONAL = {
     "sim_fp_classes": (C.c_int, [C.c_void_p, *_FPC_OUT]),
     "sim_fp_classes_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "fp_classes_of": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_size_t, C.c_uint32, *_FPC_OUT]),
+    # the latency census (include/kaboodle_latency.h; HIP library only, the oracle answers through
+    # latency.latency_census_ref)
+    "sim_latency_census": (C.c_int, [C.c_void_p, *_LATC_OUT]),
+    "sim_latency_census_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "latency_census_of": (C.c_int, [C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_size_t,
+                                    C.c_size_t, *_LATC_OUT]),
 }
 
 
@@ -360,6 +383,37 @@ def fp_classes_of(lib: SimLib, fps, running, true_fp: int, top: int = 16, arrays
     head = (device, fps.ctypes.data_as(C.POINTER(C.c_uint32)), run.ctypes.data_as(C.POINTER(C.c_uint8)), len(fps),
             int(true_fp) & 0xFFFFFFFF)
     return _fp_classes_call(lib, "fp_classes_of", head, top, arrays, len(fps))
+
+
+def _latency_census_call(lib: SimLib, name: str, head: tuple, arrays: bool, n_ids: int, n_rows: int):
+    """kb_sim_latency_census / kb_latency_census_of with the outputs of Sim.latency_census: with arrays, the four
+    arrays over `n_ids` ids and the two over `n_rows` rows."""
+    import numpy as np
+    from .latency import LatencyCensus
+    out = KbLatCensus()
+    if not arrays:
+        lib.call(name, *head, C.byref(out), None, None, None, None, 0, None, None, 0)
+        return LatencyCensus(out.as_dict())
+    mb, mn, mx = (np.zeros(n_ids, dtype=np.uint32) for _ in range(3))
+    sm, rc, rs = np.zeros(n_ids, dtype=np.uint64), np.zeros(n_rows, dtype=np.uint32), np.zeros(n_rows, dtype=np.uint64)
+    p32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+    p64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+    lib.call(name, *head, C.byref(out), p32(mb), p64(sm), p32(mn), p32(mx), n_ids, p32(rc), p64(rs), n_rows)
+    return LatencyCensus(out.as_dict(), mb, sm, mn, mx, rc, rs)
+
+
+def latency_census_of(lib: SimLib, lat, member, running, arrays: bool = True, device: int = 0):
+    """kb_latency_census_of: the latency census's kernel over host arrays (a test surface,
+    include/kaboodle_latency.h): `lat` peer-major [n_ids][n_rows] uint16 (0xFFFF = None), `member` [n_rows][n_ids],
+    `running` [n_rows]; a `LatencyCensus` with round -1.  KbError(KB_NO_DEVICE) without a GPU."""
+    import numpy as np
+    lat = np.ascontiguousarray(lat, dtype=np.uint16)
+    n_ids, n_rows = lat.shape
+    mem = np.ascontiguousarray(np.asarray(member).reshape(n_rows, n_ids) != 0, dtype=np.uint8)
+    run = np.ascontiguousarray(np.asarray(running).reshape(n_rows) != 0, dtype=np.uint8)
+    p8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))
+    head = (device, lat.ctypes.data_as(C.POINTER(C.c_uint16)), p8(mem), p8(run), n_ids, n_rows)
+    return _latency_census_call(lib, "latency_census_of", head, arrays, n_ids, n_rows)
 
 
 class Sim:
@@ -627,6 +681,23 @@ class Sim:
         """Device time of the last fp_classes() in ms (kb_sim_fp_classes_device_ms; HIP library only)."""
         v = C.c_double()
         self.lib.call("sim_fp_classes_device_ms", self.h, C.byref(v))
+        return v.value
+
+    def latency_census(self, arrays: bool = True):
+        """The latency census (include/kaboodle_latency.h): a `LatencyCensus` with `summary` (dict of
+        kb_lat_census) and, over all ids, `measured_by`, `sum_ms`, `min_ms`, `max_ms` per peer and `measured`,
+        `row_sum_ms` per row (None with arrays=False: the summary alone).  Computed on the device by
+        kb_sim_latency_census (dense handles with track_latency); a library without it (the CPU oracle) answers the
+        same call through latency.latency_census_ref, so both are compared through identical calls."""
+        if "sim_latency_census" not in self.lib.fn:
+            from .latency import latency_census_ref
+            return latency_census_ref(self, arrays)
+        return _latency_census_call(self.lib, "sim_latency_census", (self.h,), arrays, self.capacity, self.capacity)
+
+    def latency_census_device_ms(self) -> float:
+        """Device time of the last latency_census() in ms (kb_sim_latency_census_device_ms; HIP library only)."""
+        v = C.c_double()
+        self.lib.call("sim_latency_census_device_ms", self.h, C.byref(v))
         return v.value
 
     def row(self, node: int):

@@ -442,6 +442,8 @@ struct kb_sim {
   bool graph_on = false;               // env KB_WAVE_GRAPH=1
   hipGraph_t wave_graph = nullptr; hipGraphExec_t wave_exec = nullptr;
   uint64_t buf_gen = 0, wave_gen = ~0ull;
+  uint32_t* lc_buf = nullptr;          // the latency census's scratch (kb_latcensus.h), allocated by its first call
+  double lc_ms = 0;                    // device time of the last latency census
 };
 
 // allocation of this handle's device memory; row tables hold the local rows only and their pointer
@@ -2254,3 +2256,6 @@ extern "C" int kb_sim_debug_fold(kb_sim* s, const kb_fold_probe* p) {
 
 // ---- the fingerprint-class census (include/kaboodle_classes.h) -------------------------------------------
 #include "kb_classes.h"
+
+// ---- the latency census (include/kaboodle_latency.h) ------------------------------------------------------
+#include "kb_latcensus.h"

@@ -16,7 +16,8 @@ fits --max-pairs, the list of mutual pairs — the gaps that can never heal — 
 views earlier records carry, and beside it the view census's summary, which keeps what those
 views also showed: the stale entries and the ghosts (non-running ids some view still holds).  Beside the two it
 records the fingerprint-class census (include/kaboodle_classes.h): its summary and the 8 largest
-classes as (fp, size, rep).
+classes as (fp, size, rep).  With --track-latency the mesh keeps PeerInfo.latency and the record carries the latency
+census's summary too (include/kaboodle_latency.h).
 """
 from __future__ import annotations
 
@@ -57,6 +58,8 @@ def main() -> int:
     ap.add_argument("--reciprocity", action="store_true",
                     help="record the reciprocity census of the last state even when the run converged")
     ap.add_argument("--max-pairs", type=int, default=65536, help="mutual pairs listed in the result at most")
+    ap.add_argument("--track-latency", action="store_true",
+                    help="keep PeerInfo.latency (track_latency 1) and record the latency census beside the others")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import numpy as np
@@ -68,7 +71,7 @@ def main() -> int:
     cfg = SimConfig(capacity=n + max(4096, int(n * 0.001 * (F + 8) * 1.5)), initial_nodes=n,
                     init_mode=KB_INIT_CONVERGED, loss=0.01, churn=0.001, fault_end_round=F, seed=1,
                     failed_mode=KB_FAILED_SOCKET_FAITHFUL if a.mode == "sock" else KB_FAILED_SIM_SENDER,
-                    variant=KB_VARIANT_EXACT_LRU if a.lru == "exact" else 0)
+                    variant=KB_VARIANT_EXACT_LRU if a.lru == "exact" else 0, track_latency=int(a.track_latency))
     cap = int(a.cap_factor * n)
     t0 = time.time()
     traj = []
@@ -118,6 +121,10 @@ def main() -> int:
             recip["fp_classes"] = {"summary": fc.summary, "top_classes": fc.classes.tolist(),
                                    "device_ms": round(m.fp_classes_device_ms(), 4)}
             print(f"[converge {a.mode}] fp classes: {json.dumps(recip['fp_classes'])}", flush=True)
+            if cfg.track_latency:
+                recip["latency_census"] = {"summary": m.latency_census(arrays=False).summary,
+                                           "device_ms": round(m.latency_census_device_ms(), 4)}
+                print(f"[converge {a.mode}] latency census: {json.dumps(recip['latency_census'])}", flush=True)
     out = {"workload": f"configs[2]: {n} peers, converged start, 1% loss, 0.1%/round churn, faults until round {F}",
            "failed_mode": "socket_faithful" if a.mode == "sock" else "sim_sender", "fault_end_round": F,
            "a3_order": a.lru,
