@@ -15,6 +15,7 @@
 #include "kaboodle_reciprocity.h"
 #include "kaboodle_classes.h"
 #include "kaboodle_latency.h"
+#include "kaboodle_age.h"
 
 namespace kb {
 
@@ -112,6 +113,29 @@ class Mesh {
                                 arrays ? r.min_ms.data() : nullptr, arrays ? r.max_ms.data() : nullptr, r.measured_by.size(),
                                 arrays ? r.measured.data() : nullptr, arrays ? r.row_sum_ms.data() : nullptr, r.measured.size()),
           "kb_sim_latency_census");
+    return r;
+  }
+
+  // the contact-age census (kaboodle_age.h; HIP library only, sparse rows): the stamp table read mesh-wide.  Per id: the observers
+  // holding it as suspect, ancient, windowed and fresh and the latest instant any of them heard from it; per row the same
+  // four counts over its view.  arrays = false asks for the summary alone.
+  struct AgeCensus {
+    kb_age_census summary;
+    std::vector<uint32_t> suspected_by, ancient_by, windowed_by, fresh_by, suspects, ancient, windowed, fresh;
+    std::vector<int32_t> last_heard;
+  };
+  AgeCensus age_census(bool arrays = true) const {
+    AgeCensus r;
+    if (arrays) {
+      for (auto* v : {&r.suspected_by, &r.ancient_by, &r.windowed_by, &r.fresh_by, &r.suspects, &r.ancient, &r.windowed, &r.fresh})
+        v->resize(capacity_);
+      r.last_heard.resize(capacity_);
+    }
+    auto p = [&](std::vector<uint32_t>& v) { return arrays ? v.data() : nullptr; };
+    check(kb_sim_age_census(h_, &r.summary, p(r.suspected_by), p(r.ancient_by), p(r.windowed_by), p(r.fresh_by),
+                            arrays ? r.last_heard.data() : nullptr, r.last_heard.size(), p(r.suspects), p(r.ancient),
+                            p(r.windowed), p(r.fresh), r.suspects.size()),
+          "kb_sim_age_census");
     return r;
   }
 

@@ -108,6 +108,14 @@ class Mesh(Sim):
         count.  Returns a `latency.LatencyCensus`.  Needs track_latency; sparse rows and rank shards raise KbError."""
         return super().latency_census(arrays)
 
+    def age_census(self, arrays: bool = True):
+        """The stamp table mesh-wide (include/kaboodle_age.h) in one pass on the GPU: per peer how many
+        observers hold it as suspect, ancient (older than the 1-byte window), windowed and fresh (stamped within
+        SHARE_AGE rounds, so gossiped) and the latest instant any of them heard from it, per row the same four counts
+        over its view, and a histogram of the windowed entries by age.  Returns an `age.AgeCensus`.  Sparse rows,
+        unsharded or in-process shards; dense rows and rank shards raise KbError."""
+        return super().age_census(arrays)
+
 
 def latency_census_of(lat, member, running, arrays: bool = True, device: int = 0):
     """The latency census's GPU kernel over host arrays (kb_latency_census_of, a test surface): `lat` peer-major

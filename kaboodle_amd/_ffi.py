@@ -141,6 +141,24 @@ _LATC_OUT = [C.POINTER(KbLatCensus), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64
              C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t]
 
 
+class KbAgeCensus(C.Structure):
+    """kb_age_census (include/kaboodle_age.h)."""
+    _fields_ = [("round", C.c_int32), ("observers", C.c_uint32), ("cells", C.c_uint64), ("suspects", C.c_uint64),
+                ("ancient", C.c_uint64), ("windowed", C.c_uint64), ("fresh", C.c_uint64), ("dead_suspects", C.c_uint64),
+                ("dead_ancient", C.c_uint64), ("dead_windowed", C.c_uint64), ("dead_fresh", C.c_uint64),
+                ("unheard_ids", C.c_uint32), ("oldest_heard_id", C.c_uint32), ("oldest_heard", C.c_int32),
+                ("pad", C.c_uint32), ("hist", C.c_uint64 * 256), ("reserved", C.c_uint64 * 4)]
+
+    def as_dict(self) -> dict:
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n not in ("reserved", "hist", "pad")}
+        d["hist"] = [int(x) for x in self.hist]
+        return d
+
+
+_AGEC_OUT = [C.POINTER(KbAgeCensus), *[C.POINTER(C.c_uint32)] * 4, C.POINTER(C.c_int32), C.c_size_t,
+             *[C.POINTER(C.c_uint32)] * 4, C.c_size_t]
+
+
 KB_FOLD_TICK, KB_FOLD_FP_ALL, KB_FOLD_FP_ONE, KB_FOLD_THREAD = 0, 1, 2, 3   # kb_fold_probe.path
 NSEG = 64                        # fingerprint checkpoints per row
 
@@ -311,6 +329,9 @@ _OPTIONAL = {
     "sim_latency_census_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "latency_census_of": (C.c_int, [C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_size_t,
                                     C.c_size_t, *_LATC_OUT]),
+    # the contact-age census (include/kaboodle_age.h; HIP library only, the oracle answers through age.age_census_ref)
+    "sim_age_census": (C.c_int, [C.c_void_p, *_AGEC_OUT]),
+    "sim_age_census_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
 }
 
 
@@ -414,6 +435,23 @@ def latency_census_of(lib: SimLib, lat, member, running, arrays: bool = True, de
     p8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))
     head = (device, lat.ctypes.data_as(C.POINTER(C.c_uint16)), p8(mem), p8(run), n_ids, n_rows)
     return _latency_census_call(lib, "latency_census_of", head, arrays, n_ids, n_rows)
+
+
+def _age_census_call(lib: SimLib, name: str, head: tuple, arrays: bool, n_ids: int, n_rows: int):
+    """kb_sim_age_census with the outputs of Sim.age_census: with arrays, the five arrays over
+    `n_ids` ids and the four over `n_rows` rows."""
+    import numpy as np
+    from .age import AgeCensus
+    out = KbAgeCensus()
+    if not arrays:
+        lib.call(name, *head, C.byref(out), None, None, None, None, None, 0, None, None, None, None, 0)
+        return AgeCensus(out.as_dict())
+    by = [np.zeros(n_ids, dtype=np.uint32) for _ in range(4)]
+    lh = np.zeros(n_ids, dtype=np.int32)
+    rw = [np.zeros(n_rows, dtype=np.uint32) for _ in range(4)]
+    p32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+    lib.call(name, *head, C.byref(out), *map(p32, by), lh.ctypes.data_as(C.POINTER(C.c_int32)), n_ids, *map(p32, rw), n_rows)
+    return AgeCensus(out.as_dict(), *by, lh, *rw)
 
 
 class Sim:
@@ -693,6 +731,23 @@ class Sim:
             from .latency import latency_census_ref
             return latency_census_ref(self, arrays)
         return _latency_census_call(self.lib, "sim_latency_census", (self.h,), arrays, self.capacity, self.capacity)
+
+    def age_census(self, arrays: bool = True):
+        """The contact-age census (include/kaboodle_age.h): an `AgeCensus` with `summary` (dict of kb_age_census)
+        and, over all ids, `suspected_by`, `ancient_by`, `windowed_by`, `fresh_by`, `last_heard` per peer and
+        `suspects`, `ancient`, `windowed`, `fresh` per row (None with arrays=False).  Computed on the device by
+        kb_sim_age_census (sparse rows; dense handles raise KbError); a library without it (the CPU oracle) answers the same call through age.age_census_ref,
+        so both are compared through identical calls."""
+        if "sim_age_census" not in self.lib.fn:
+            from .age import age_census_ref
+            return age_census_ref(self, arrays)
+        return _age_census_call(self.lib, "sim_age_census", (self.h,), arrays, self.capacity, self.capacity)
+
+    def age_census_device_ms(self) -> float:
+        """Device time of the last age_census() in ms (kb_sim_age_census_device_ms; HIP library only)."""
+        v = C.c_double(0)
+        self.lib.call("sim_age_census_device_ms", self.h, C.byref(v))
+        return v.value
 
     def latency_census_device_ms(self) -> float:
         """Device time of the last latency_census() in ms (kb_sim_latency_census_device_ms; HIP library only)."""

@@ -275,7 +275,9 @@ static int cs_dense(kb_sim* s, CsPart& p) {
   return KB_OK;
 }
 
-static int cs_sparse(SpSim* S, CsPart& p) {
+// the sparse pass; its device time goes to *ms and the handle's own figure is left alone (the contact-age census
+// reuses the pass, kb_agecensus.h)
+static int cs_sparse_pass(SpSim* S, CsPart& p, double* ms) {
   (void)hipSetDevice(S->device);
   const SpDev& d = S->d;
   const uint32_t C = S->C, R = S->R;
@@ -294,9 +296,10 @@ static int cs_sparse(SpSim* S, CsPart& p) {
   HIPCHK(hipGetLastError());
   const int rc = cs_collect(p, C, S->lo, R, a.kb, a.rowc, d.alive, d.ext, S->st);
   if (rc) return rc;
-  S->cs_ms = tm.ms(); p.ms += S->cs_ms;
+  *ms = tm.ms(); p.ms += *ms;
   return KB_OK;
 }
+static int cs_sparse(SpSim* S, CsPart& p) { return cs_sparse_pass(S, p, &S->cs_ms); }
 
 // the O(ids) reductions of the summary, on the host
 static void cs_summary(const CsPart& p, uint32_t C, int32_t round, kb_census* out, uint32_t* missing, uint32_t* stale) {

@@ -444,6 +444,7 @@ struct kb_sim {
   uint64_t buf_gen = 0, wave_gen = ~0ull;
   uint32_t* lc_buf = nullptr;          // the latency census's scratch (kb_latcensus.h), allocated by its first call
   double lc_ms = 0;                    // device time of the last latency census
+  double ag_ms = 0;                    // device time of the last contact-age census
 };
 
 // allocation of this handle's device memory; row tables hold the local rows only and their pointer
@@ -2259,3 +2260,6 @@ extern "C" int kb_sim_debug_fold(kb_sim* s, const kb_fold_probe* p) {
 
 // ---- the latency census (include/kaboodle_latency.h) ------------------------------------------------------
 #include "kb_latcensus.h"
+
+// ---- the contact-age census (include/kaboodle_age.h) -------------------------------------------------------
+#include "kb_agecensus.h"

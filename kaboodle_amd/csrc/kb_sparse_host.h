@@ -79,6 +79,8 @@ struct SpSim {
   uint64_t host_syncs = 0;
   uint32_t* cs_buf = nullptr;                       // the census's scratch (kb_census.h), allocated by the first census
   double cs_ms = 0;                                 // device time of the last census
+  uint32_t* ag_buf = nullptr;                       // the contact-age census's scratch (kb_agecensus.h), allocated by its first call
+  double ag_ms = 0;                                 // device time of the last contact-age census
   // external peers
   std::vector<uint8_t> h_ext;
   size_t n_ext = 0;
