@@ -93,6 +93,33 @@ class Mesh(Sim):
             for k in subs:                        # closed channels are dropped (events.rs:29-38)
                 subs[k] = [c for c in subs[k] if not c.closed]
 
+    def save(self, path: str) -> int:
+        """Write the mesh's snapshot (Sim.snapshot) to `path`; returns its length.  The bytes go to a
+        temporary name in the same directory and are renamed, so a killed process never leaves half a file under
+        the final name."""
+        blob = self.snapshot()
+        tmp = f"{path}.tmp.{os.getpid()}"
+        try:
+            with open(tmp, "wb") as f:
+                f.write(blob)
+                f.flush()
+                os.fsync(f.fileno())
+            os.replace(tmp, path)
+        except BaseException:
+            if os.path.exists(tmp):
+                os.unlink(tmp)
+            raise
+        return len(blob)
+
+    @classmethod
+    def load(cls, path: str, shards: int = 0, device: int = -1) -> "Mesh":
+        """A new mesh in the state `save` wrote, unsharded or as `shards` in-process row shards (any layout may
+        have written the file).  Channels and observers are not carried: subscribe again."""
+        with open(path, "rb") as f:
+            blob = f.read()
+        m = cls.restore(lib(), blob, shards=shards, device=device)
+        m._subs = {}
+        return m
 
     def fp_classes(self, top: int = 16, arrays: bool = True):
         """Which camps the views fall into (include/kaboodle_classes.h): the running rows grouped

@@ -159,6 +159,21 @@ _AGEC_OUT = [C.POINTER(KbAgeCensus), *[C.POINTER(C.c_uint32)] * 4, C.POINTER(C.c
              *[C.POINTER(C.c_uint32)] * 4, C.c_size_t]
 
 
+KB_SNAPSHOT_VERSION = 1
+
+
+class KbSnapshotInfo(C.Structure):
+    """kb_snapshot_info (include/kaboodle_snapshot.h)."""
+    _fields_ = [("format_version", C.c_uint32), ("abi_version", C.c_uint32), ("cfg", KbConfig), ("round", C.c_int32),
+                ("alive", C.c_uint32), ("entries", C.c_uint64), ("bytes", C.c_uint64), ("payload_crc32", C.c_uint32),
+                ("reserved", C.c_uint32 * 7)]
+
+    def as_dict(self) -> dict:
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n not in ("reserved", "cfg")}
+        d["cfg"] = {n: int(getattr(self.cfg, n)) for n, _ in KbConfig._fields_ if n != "reserved"}
+        return d
+
+
 KB_FOLD_TICK, KB_FOLD_FP_ALL, KB_FOLD_FP_ONE, KB_FOLD_THREAD = 0, 1, 2, 3   # kb_fold_probe.path
 NSEG = 64                        # fingerprint checkpoints per row
 
@@ -249,6 +264,16 @@ class SimConfig:
         c.sparse_row_cap, c.stat_flags = self.sparse_row_cap, self.stat_flags
         return c
 
+    @classmethod
+    def from_c(cls, c: KbConfig) -> "SimConfig":
+        """The mirror of a kb_config (a snapshot's): to_c() of the result gives the same thresholds back."""
+        return cls(capacity=c.capacity, initial_nodes=c.initial_nodes, init_mode=c.init_mode, seed=c.seed,
+                   loss=c.loss_threshold / 2**32, churn=c.churn_threshold / 2**32, fault_end_round=c.fault_end_round,
+                   max_waves=c.max_waves, failed_mode=c.failed_mode, id_len=c.id_len, partition_groups=c.partition_groups,
+                   partition_start=c.partition_start, partition_end=c.partition_end, device=c.device,
+                   debug_flags=c.debug_flags, track_latency=c.track_latency, variant=c.variant,
+                   sparse_row_cap=c.sparse_row_cap, stat_flags=c.stat_flags)
+
 
 _SIGS = {
     "sim_create": (C.c_int, [C.POINTER(KbConfig), C.POINTER(C.c_void_p)]),
@@ -332,6 +357,11 @@ _OPTIONAL = {
     # the contact-age census (include/kaboodle_age.h; HIP library only, the oracle answers through age.age_census_ref)
     "sim_age_census": (C.c_int, [C.c_void_p, *_AGEC_OUT]),
     "sim_age_census_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    # snapshot and restore (include/kaboodle_snapshot.h; HIP library only)
+    "snapshot_info_of": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(KbSnapshotInfo)]),
+    "sim_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "sim_restore": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "sim_snapshot_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
 }
 
 
@@ -747,6 +777,41 @@ class Sim:
         """Device time of the last age_census() in ms (kb_sim_age_census_device_ms; HIP library only)."""
         v = C.c_double(0)
         self.lib.call("sim_age_census_device_ms", self.h, C.byref(v))
+        return v.value
+
+    def snapshot(self) -> bytes:
+        """The mesh's state after the last completed round as one byte string (kb_sim_snapshot,
+        include/kaboodle_snapshot.h): canonical, the same bytes from an unsharded handle and a group of shards.
+        Sparse rows; dense rows, rank shards and a handle with calls queued for the next round raise KbError."""
+        n = C.c_uint64(0)
+        self.lib.call("sim_snapshot", self.h, None, 0, C.byref(n))
+        buf = C.create_string_buffer(n.value)
+        self.lib.call("sim_snapshot", self.h, buf, n.value, C.byref(n))
+        return buf.raw[: n.value]
+
+    @classmethod
+    def restore(cls, lib: SimLib, blob: bytes, shards: int = 0, device: int = -1) -> "Sim":
+        """A new handle in the state of `blob` (kb_sim_restore): shards 0 or 1 unsharded, 2..8 an in-process group
+        of row shards, whatever layout wrote the snapshot.  It continues bit for bit as the source would; observers
+        (watch) and undrained outputs are not carried."""
+        info = KbSnapshotInfo()
+        lib.call("snapshot_info_of", blob, len(blob), C.byref(info))
+        h = C.c_void_p()
+        lib.call("sim_restore", blob, len(blob), shards, device, C.byref(h))
+        self = cls.__new__(cls)
+        self.lib, self.cfg = lib, SimConfig.from_c(info.cfg)
+        self.cfg.device = device
+        self._c = self.cfg.to_c()
+        self.h = h
+        self.capacity = self.cfg.capacity
+        self.external = set()
+        return self
+
+    def snapshot_device_ms(self) -> float:
+        """Device time of the last snapshot()'s pack, or of the restore that made this handle, in ms
+        (kb_sim_snapshot_device_ms)."""
+        v = C.c_double(0)
+        self.lib.call("sim_snapshot_device_ms", self.h, C.byref(v))
         return v.value
 
     def latency_census_device_ms(self) -> float:

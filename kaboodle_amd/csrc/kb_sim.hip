@@ -445,6 +445,7 @@ struct kb_sim {
   uint32_t* lc_buf = nullptr;          // the latency census's scratch (kb_latcensus.h), allocated by its first call
   double lc_ms = 0;                    // device time of the last latency census
   double ag_ms = 0;                    // device time of the last contact-age census
+  double sn_ms = 0;                    // device time of the last snapshot pack, or of the restore that made the handle
 };
 
 // allocation of this handle's device memory; row tables hold the local rows only and their pointer
@@ -2263,3 +2264,6 @@ extern "C" int kb_sim_debug_fold(kb_sim* s, const kb_fold_probe* p) {
 
 // ---- the contact-age census (include/kaboodle_age.h) -------------------------------------------------------
 #include "kb_agecensus.h"
+
+// ---- snapshot and restore (include/kaboodle_snapshot.h) ----------------------------------------------------
+#include "kb_snapshot.h"

@@ -88,6 +88,11 @@ struct SpSim {
   std::vector<uint32_t> inj_join;                    // external peers' Join broadcasts for the next round
   XRec* d_inj = nullptr; uint32_t* d_inj_ids = nullptr; size_t d_inj_cap = 0, d_inj_ids_cap = 0;
   std::vector<kb_unicast> xq; std::vector<uint32_t> xq_ids;
+  // snapshot and restore (kb_snapshot.h): the scratch is allocated by the first call
+  unsigned long long* sn_fix = nullptr;             // the rows' entry offsets, the scan's tile sums, the canonical fingerprints
+  uint32_t* sn_buf = nullptr; size_t sn_cap = 0;    // the packed entries, grown on demand
+  uint64_t sn_total = 0;                            // entries of this handle's rows at the last scan
+  double sn_ms = 0;                                 // device time of the last pack or unpack
 };
 
 static int sp_err_status(uint32_t e) {

@@ -8,6 +8,10 @@ the kernel breakdown and the property checks of tests/test_gpu_sparse_big.py on 
 Reconvergence after the heal: --fault-end R ends the loss at round R, --until-converged runs until every live
 view's fingerprint equals the true set's (or --rounds / --budget-s).
 
+A long run can outlive its process: --checkpoint PATH --checkpoint-every N writes the mesh's
+snapshot to PATH after every N-th round (renamed into place), --resume PATH continues from such a file; the
+records of a resumed run carry the round it resumed from.
+
 The Failed lists' lost deliveries are not counted by default (KB_STAT_NO_SF_FAILED_DROPS): in socket_faithful mode
 a Failed broadcast changes no state, so the count is a statistic only, and at 4M it is one Philox
 word per (receiver, entry), ≈ 10^12 a round, 96 % of the round.  --count-sf-failed-drops counts them (the
@@ -65,15 +69,20 @@ def check_invariants(st: dict, n: int, rounds: int) -> list[str]:
 
 def run(n: int, rounds: int, every: int, row_cap: int, check_rows: int, seed: int = 9, verbose: bool = True,
         fault_end: int = -1, stat_flags: int = 0, until_converged: bool = False, budget_s: float = 0.0,
-        print_every: int = 1, fp_every: int = 4) -> dict:
+        print_every: int = 1, fp_every: int = 4, checkpoint: str = "", checkpoint_every: int = 0, resume: str = "") -> dict:
     import kaboodle_amd
     import parity
     from kaboodle_amd._ffi import Sim
     lib = kaboodle_amd.lib()                                  # honours KB_LIB_PATH (A/B builds)
     case = scenario(n, every, seed, row_cap, fault_end=fault_end, stat_flags=stat_flags)
     t0 = time.time()
-    g = Sim(lib, case["cfg"])
+    if resume:                                               # the state a --checkpoint run left (same scenario arguments)
+        with open(resume, "rb") as f:
+            g = Sim.restore(lib, f.read())
+    else:
+        g = Sim(lib, case["cfg"])
     t_create = time.time() - t0
+    r0 = g.stats()["round"]                                  # 0, or the round a resumed run continues at
     g.set_profiling(1)
     rng = np.random.default_rng(seed)
     traj, prev = [], g.stats()
@@ -81,18 +90,23 @@ def run(n: int, rounds: int, every: int, row_cap: int, check_rows: int, seed: in
     fails = []
     heal = case["cfg"].partition_end
     converged_round, stopped_by, t_start = None, "rounds", time.time()
-    for r in range(rounds):
+    r = r0 - 1
+    for r in range(r0, rounds):
         parity.apply_events((g,), case, r)
         t = time.time()
         g.step(1)
         dt = time.time() - t
         all_ms.append(dt * 1e3)
+        if checkpoint and checkpoint_every and (r + 1) % checkpoint_every == 0:
+            kaboodle_amd.Mesh.save(g, checkpoint)
         st = g.stats()
         rec = {"round": r, "ms": round(dt * 1e3, 1), "agree": st["agree"],
                "failed_bcasts": st["bcast_failed"] - prev["bcast_failed"],
                "drop_bcast": st["drop_bcast"] - prev["drop_bcast"], "drop_partition": st["drop_partition"] - prev["drop_partition"],
                "sent": sum(st[k] - prev[k] for k in ("sent_ping", "sent_ping_req", "sent_ack", "sent_known_peers", "sent_kpr")),
                "kpr": st["sent_kpr"] - prev["sent_kpr"], "oversize": st["drop_oversize"] - prev["drop_oversize"]}
+        if resume:
+            rec["resumed_from"] = r0
         done = until_converged and r >= heal and st["agree"] == st["alive"]
         if done:
             converged_round, stopped_by = r, "converged"
@@ -138,10 +152,12 @@ def run(n: int, rounds: int, every: int, row_cap: int, check_rows: int, seed: in
     kb = g.kernel_breakdown()
     round_ms, nr = g.kernel_time(1)
     g.close()
+    ran = max(len(all_ms), 1)                                # rounds this process simulated (all of them unless resumed)
     return {"nodes": n, "rounds": rounds, "row_cap": row_cap, "create_s": round(t_create, 1), "fault_end_round": fault_end,
+            **({"resumed_from": r0} if resume else {}),
             "stat_flags": stat_flags, "converged_round": converged_round, "stopped_by": stopped_by,
             "wall_s": round(time.time() - t_start, 1), "bench_line": bench_line, "trajectory": traj,
-            "kernels_ms_per_round": {k: round(v["ms"] / rounds, 3) for k, v in sorted(kb.items(), key=lambda x: -x[1]["ms"])},
+            "kernels_ms_per_round": {k: round(v["ms"] / ran, 3) for k, v in sorted(kb.items(), key=lambda x: -x[1]["ms"])},
             "gpu_round_ms_mean": round(round_ms / max(nr, 1), 2), "final_stats": st, "failures": fails}
 
 
@@ -239,11 +255,15 @@ def main() -> int:
     ap.add_argument("--fp-every", type=int, default=4)
     ap.add_argument("--count-sf-failed-drops", action="store_true")
     ap.add_argument("--no-sf-failed-drops", action="store_true", help="the default (kept for older scripts)")
+    ap.add_argument("--checkpoint", default="", help="write the mesh's snapshot here (with --checkpoint-every)")
+    ap.add_argument("--checkpoint-every", type=int, default=0, help="after every N-th round (0: never)")
+    ap.add_argument("--resume", default="", help="continue from a --checkpoint file of the same scenario")
     a = ap.parse_args()
     from kaboodle_amd._ffi import KB_STAT_NO_SF_FAILED_DROPS
     res = run(a.nodes, a.rounds, a.every, a.row_cap, a.check_rows, fault_end=a.fault_end,
               stat_flags=0 if a.count_sf_failed_drops else KB_STAT_NO_SF_FAILED_DROPS, until_converged=a.until_converged,
-              budget_s=a.budget_s, print_every=a.print_every, fp_every=a.fp_every)
+              budget_s=a.budget_s, print_every=a.print_every, fp_every=a.fp_every, checkpoint=a.checkpoint,
+              checkpoint_every=a.checkpoint_every, resume=a.resume)
     res["scenario"] = ("configs[4]: converged start, 5% loss" + (f" until round {a.fault_end}" if a.fault_end >= 0 else "")
                        + ", 2-way partition rounds 3-11, heal at 12 (every "
                        f"{a.every}th peer pings across), socket_faithful, sparse rows on one MI355X"
