@@ -124,8 +124,11 @@ enum {
                                 (source shard, joiner) (A/B and parity surface)          */
   KB_DBG_A3X_KPL8 = 256u,    /* KB_VARIANT_EXACT_LRU: A3 by the kernel of 128K-512K-id rows (eight block bounds
                                 per lane) at any width                                                 */
-  KB_DBG_A3X_WIDE = 512u     /* KB_VARIANT_EXACT_LRU: A3 by the one-pass kernel of rows above 512K ids at any
+  KB_DBG_A3X_WIDE = 512u,    /* KB_VARIANT_EXACT_LRU: A3 by the one-pass kernel of rows above 512K ids at any
                                 width (wins over KB_DBG_A3X_KPL8)                                      */
+  KB_DBG_WAVE0_SERIAL = 1024u /* wave 0 of a round with joiners keeps the one KnownPeers launch before the
+                                in-order handlers instead of the BIG groups on the side stream
+                                (A/B and parity surface)                               */
 };
 
 /* Per-peer state as reported by peer_states() (PeerState, src/structs.rs:27-41). */

@@ -344,7 +344,7 @@ struct kb_sim {
   // side stream: kernels off the round's critical path (the running set's fingerprint, the latency sweep)
   // run beside it, forked from and joined back into st by events
   hipStream_t st2 = nullptr;
-  hipEvent_t ev_fork[3] = {nullptr, nullptr, nullptr}, ev_join[3] = {nullptr, nullptr, nullptr};   // side work 0-2
+  hipEvent_t ev_fork[4] = {nullptr, nullptr, nullptr, nullptr}, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};   // side work 0-3
   uint32_t C, W, S;                    // capacity, row stride, row-sweep column splits
   // row shard: this handle holds rows [lo, hi) of the mesh, R = hi - lo
   uint32_t lo, hi, R;
@@ -388,6 +388,8 @@ struct kb_sim {
   uint32_t* nresp; uint32_t* paysum; uint32_t* nbase; uint32_t* resp_off;
   uint32_t* resp_nodes; uint32_t* bf_gid; uint8_t* bf_dep;
   uint32_t* slow;                      // the nodes of a wave k_proc_fast leaves to k_proc
+  uint32_t* defer = nullptr;           // split wave 0: the BIG KnownPeers groups' destinations, handled after the join
+  uint32_t* w0ctr = nullptr;           // its counters (W0_*: deferred nodes, k_proc's tickets)
   uint16_t* lat_col;                   // [C] one node's latencies (peer_states), track_latency only
   uint32_t* fnamed;                    // [NWR] peers named by the round's Failed list (track_latency only)
   uint32_t* resp_scratch; size_t resp_scratch_words;
@@ -626,7 +628,7 @@ static void destroy_shard(kb_sim* s) {
   if (s->wave_graph) (void)hipGraphDestroy(s->wave_graph);
   if (s->st) (void)hipStreamDestroy(s->st);
   if (s->st2) (void)hipStreamDestroy(s->st2);
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < 4; ++k) {
     if (s->ev_fork[k]) (void)hipEventDestroy(s->ev_fork[k]);
     if (s->ev_join[k]) (void)hipEventDestroy(s->ev_join[k]);
   }
@@ -641,7 +643,7 @@ static int create_shard(const kb_config* cfg, int rank, int world, Xfer* xf, kb_
   if (cfg->capacity == 0 || cfg->capacity > 7800000u || cfg->initial_nodes > cfg->capacity || cfg->id_len > MAXID ||
       cfg->max_waves == 0 || cfg->max_waves > 64) { seterr("config out of range"); delete xf; return KB_INVALID_ARGUMENT; }
   if (cfg->stat_flags) { seterr("kb_config.stat_flags: sparse rows and the oracle only"); delete xf; return KB_INVALID_ARGUMENT; }
-  if (cfg->variant && cfg->variant != KB_VARIANT_EXACT_LRU) { seterr(cfg->variant == KB_VARIANT_SPARSE_ROWS ? "sparse rows run unsharded (kb_sim_create)" : "semantic variants other than KB_VARIANT_SPARSE_ROWS are measurement-only (CPU oracle)"); delete xf; return KB_INVALID_ARGUMENT; }
+  if (cfg->variant && cfg->variant != KB_VARIANT_EXACT_LRU) { seterr("semantic variants other than KB_VARIANT_SPARSE_ROWS are measurement-only (CPU oracle)"); delete xf; return KB_INVALID_ARGUMENT; }
   const uint32_t C = cfg->capacity;
   const uint32_t rows_per = (C + (uint32_t)world - 1) / (uint32_t)world;
   if (world < 1 || world > (int)XMAX || rank < 0 || rank >= world || (uint64_t)(world - 1) * rows_per >= C) {
@@ -725,7 +727,7 @@ constexpr uint32_t KB_FOLD_WAVES = 16384;                            // fold wav
   AR(s->bs.join, 1); AR(s->bs.nfail, 1); AR(s->bs.fail, SLOTS); AR(s->join_off, 1); AR(s->fail_off, 1);
   A(s->scan_tot, 32); A(s->rr, 4); A(s->scan_tiles, 5 * ((std::max<size_t>(C, (size_t)world * R) + 1023) / 1024) + 5);
   AR(s->nresp, 1); AR(s->paysum, 1); AR(s->nbase, 1); AR(s->resp_off, 1);
-  A(s->resp_nodes, R); A(s->bf_gid, (size_t)C * SLOTS); A(s->bf_dep, (size_t)C * SLOTS); A(s->slow, R);
+  A(s->resp_nodes, R); A(s->bf_gid, (size_t)C * SLOTS); A(s->bf_dep, (size_t)C * SLOTS); A(s->slow, R); A(s->defer, R); A(s->w0ctr, W0_WORDS);
   AR(s->ro.part, 10);
   if (xf) {
     XState& x = s->xs;
@@ -754,7 +756,7 @@ constexpr uint32_t KB_FOLD_WAVES = 16384;                            // fold wav
   s->wc.msg_cap = s->msg_cap; s->wc.pay_cap = s->pay_cap;
   if (hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess) { destroy_shard(s); seterr("stream"); return KB_IO_ERROR; }
   if (hipStreamCreateWithFlags(&s->st2, hipStreamNonBlocking) != hipSuccess) { destroy_shard(s); seterr("stream"); return KB_IO_ERROR; }
-  for (int k = 0; k < 3; ++k)
+  for (int k = 0; k < 4; ++k)
     if (hipEventCreateWithFlags(&s->ev_fork[k], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&s->ev_join[k], hipEventDisableTiming) != hipSuccess) { destroy_shard(s); seterr("events"); return KB_IO_ERROR; }
   if (hipHostMalloc((void**)&s->h_pin, 4 * PIN_WORDS, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
@@ -1159,22 +1161,44 @@ static int launch_waves(kb_sim* s, int32_t rk) {
       HIPCHK(hipMemsetAsync(d.ctr + C_DBG_INS, 0, 52, st));
       HIPCHK(hipMemsetAsync(d.ctr + C_DBG_SLOW_LONG, 0, 20, st));
     }
+    // wave 0 of a round with joiners: their BIG groups overlap the in-order handlers of every other node.  Not
+    // under graph capture (the window stays one chain there), KB_DEBUG_WAVES (its read-backs follow st only) or
+    // KB_DBG_WAVE0_SERIAL
+    const bool split = w == 0 && s->nj > 0 && !s->xf && !s->graph_on && !s->capturing && !s->debug_waves &&
+                       !(d.dbg & KB_DBG_WAVE0_SERIAL);
     {  // the KnownPeers groups: BIG ones KP_COLS workgroups per destination group (one per column part),
        // then the small ones (a wave per destination), which also set up nb.cap / nb.cnt
       const uint32_t ks = (d.NWR <= KP_LDS_WORDS && !(d.dbg & KB_DBG_KP_HBM)) ? KP_COLS : 1u;
       const uint32_t groups = std::max<uint32_t>(1u, std::min<uint32_t>((R + 1023) / 1024 * (ks > 1 ? 2u : 1u), 512u / ks));
       constexpr uint32_t KB_KPS_PER_CU = 1;        // small-group workgroups per CU (2: no faster, profiles/r04u2_ab_unrolls.txt)
       const uint32_t small = std::max<uint32_t>((R + 1023) / 1024, KB_KPS_PER_CU * s->ncu);
-      klaunch(s, KI_KP, k_kp, dim3(ks * groups + small), dim3(1024), (uint32_t)kp_lds_bytes(d.NWR), d, ib, s->wc, r,
-              nb, ks * groups);
+      if (split) {
+        // split wave 0: the BIG groups (the round's joiners) alone on the side stream, from here
+        // (the inboxes are placed) to the next wave's k_route; the small groups and the outbox setup stay here
+        side_fork(s, 3);
+        klaunch_on(s, s->st2, KI_KP, k_kp, dim3(ks * groups), dim3(1024), (uint32_t)kp_lds_bytes(d.NWR), d, ib, s->wc, r, nb,
+                   ks * groups, (uint32_t*)nullptr);
+        side_done(s, 3);
+        klaunch(s, KI_KP, k_kp, dim3(small), dim3(1024), 0, d, ib, s->wc, r, nb, 0u, s->w0ctr);
+      } else
+        klaunch(s, KI_KP, k_kp, dim3(ks * groups + small), dim3(1024), (uint32_t)kp_lds_bytes(d.NWR), d, ib, s->wc, r,
+                nb, ks * groups, (uint32_t*)nullptr);
     }
-    // inbox sorts + the KPR oversize probe, and the fast handlers
+    // inbox sorts + the KPR oversize probe, and the fast handlers (split: a BIG group's destination goes to `defer`)
     klaunch(s, KI_SORTFAST, k_sortfast, dim3(SORT_GROUPS + (R + SORTFAST_T - 1) / SORTFAST_T), dim3(SORTFAST_T), 0, d, ib, nb,
-            s->wc, r, s->slow, SORT_GROUPS);
+            s->wc, r, s->slow, SORT_GROUPS, split ? s->defer : (uint32_t*)nullptr, split ? s->w0ctr : (uint32_t*)nullptr);
     // persistent: as many workgroups as stay resident (204 VGPRs: 2 waves/SIMD, 2 workgroups per CU).
     // A larger grid only queues workgroups that read the node count and exit, which set a ~40 us floor
     // on the late waves with few nodes.
-    klaunch(s, KI_PROC, k_proc, dim3(std::min<uint32_t>(4096, (KB_PROC_WPE > 2 ? KB_PROC_WPE : 2) * s->ncu)), dim3(256), 0, d, ib, nb, s->wc, r, s->slow);
+    klaunch(s, KI_PROC, k_proc, dim3(std::min<uint32_t>(4096, (KB_PROC_WPE > 2 ? KB_PROC_WPE : 2) * s->ncu)), dim3(256), 0, d, ib, nb, s->wc, r,
+            (const uint32_t*)s->slow, (const uint32_t*)(d.ctr + C_SLOW), split ? s->w0ctr + W0_TICKET : (uint32_t*)nullptr);
+    if (split) {
+      // after the join: the BIG groups' destinations, in order behind their groups (the joiners that also got a
+      // Ping, Ack or KPR; the others only have their counters cleared)
+      side_join(s, 3);
+      klaunch(s, KI_PROC, k_proc, dim3(std::min<uint32_t>(2 * s->ncu, std::max<uint32_t>(1u, (s->nj + 3) / 4))), dim3(256), 0, d, ib, nb,
+              s->wc, r, (const uint32_t*)s->defer, (const uint32_t*)(s->w0ctr + W0_DEFER), (uint32_t*)nullptr);
+    }
     if (s->debug_waves) {
       uint32_t dbg[13], slow = 0;
       HIPCHK(hipMemcpyAsync(dbg, d.ctr + C_DBG_INS, 52, hipMemcpyDeviceToHost, st));

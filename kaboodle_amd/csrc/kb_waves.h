@@ -16,7 +16,9 @@ struct WaveCtl {
 
 // The per-destination counters of a wave are zero outside the wave's active nodes.  Whoever handles
 // an active node last in the wave puts them back to zero: k_proc_fast for the nodes it finishes (or
-// that have no in-order delivery), k_proc for the rest.  No clearing launch per wave.
+// that have no in-order delivery), k_proc for the rest.  No clearing launch per wave.  (Wave 0 with its BIG
+// KnownPeers groups on the side stream, DESIGN.md §3.2: a BIG destination's counters are still read by its
+// group while the in-order handlers run, so the deferred k_proc pass after the join clears them.)
 __device__ inline void wave_ctr_clear(const WaveCtl& wc, uint32_t i) {
   wc.cnt1[i] = 0; wc.bnd[i] = 0; wc.bpay[i] = 0; wc.cursor[i] = 0;
   wc.kcnt[i] = 0; wc.kpay[i] = 0; wc.kcur[i] = 0;
@@ -682,14 +684,19 @@ __device__ __attribute__((always_inline)) inline void kp_group_body(const Dev& d
 // k_kp's last nblk workgroups: at least one per CU, since a round of the converged start's first
 // SHARE_AGE rounds delivers ~24K replies of a few hundred ids at 64K peers in one wave.)
 constexpr uint32_t KB_KPS_UNROLL = 4;
+constexpr uint32_t W0_DEFER = 0, W0_TICKET = 1, W0_WORDS = 2;   // split wave 0's counters: deferred nodes, k_proc's tickets
 constexpr int KPS_UNROLL = KB_KPS_UNROLL;
 __device__ __attribute__((always_inline)) inline void kp_small_body(const Dev& d, const OutBuf& ib, const WaveCtl& wc, int32_t r,
-                                                                   const OutBuf& nb, uint32_t bid, uint32_t nblk) {
+                                                                   const OutBuf& nb, uint32_t bid, uint32_t nblk,
+                                                                   uint32_t* w0) {
   __shared__ uint32_t s_list[1024], s_nl;
   const uint32_t t = threadIdx.x, T = blockDim.x, nwv = T >> 6, wv = t >> 6, l = lane();
   // the next outbox of every local row: capacity = the wave's reservation, empty (was a copy + memset)
   for (uint32_t i = d.lo + bid * T + t; i < d.hi; i += nblk * T) { nb.cap[i] = wc.bnd[i]; nb.cnt[i] = 0; }
-  if (bid == 0 && t == 0) d.ctr[C_SLOW] = 0;             // the fast handlers list this wave's slow nodes afresh
+  if (bid == 0 && t == 0) {
+    d.ctr[C_SLOW] = 0;                                   // the fast handlers list this wave's slow nodes afresh
+    if (w0) { w0[W0_DEFER] = 0; w0[W0_TICKET] = 0; }     // and (split wave 0) its deferred nodes; k_proc's tickets
+  }
   const uint32_t nact = d.ctr[C_ACTIVE];
   const uint8_t old = enc(r - SHARE_AGE, r), now = enc(r, r);
   const uint32_t kpb = (d.dbg & KB_DBG_KP_BIG_SMALL) ? 0u : KP_BIG;
@@ -794,10 +801,13 @@ __device__ __attribute__((always_inline)) inline void kp_small_body(const Dev& d
 // The KnownPeers group of every destination of the wave in ONE launch: workgroups [0, nbig) serve the
 // BIG groups (KP_COLS per destination group, bitset in LDS), the rest the small groups (a wave per
 // destination) and set up the next outbox.  The two kinds never share a destination.
-__global__ __launch_bounds__(1024) void k_kp(Dev d, OutBuf ib, WaveCtl wc, int32_t r_arg, OutBuf nb, uint32_t nbig) {
+// Split wave 0 launches the two kinds apart: the BIG groups alone on the side stream (nbig = the
+// grid), the rest on the main stream (nbig = 0, w0 = the split's counters, cleared with C_SLOW).
+__global__ __launch_bounds__(1024) void k_kp(Dev d, OutBuf ib, WaveCtl wc, int32_t r_arg, OutBuf nb, uint32_t nbig,
+                                             uint32_t* w0) {
   const int32_t r = round_of(d, r_arg);
   if (blockIdx.x < nbig) kp_group_body<true>(d, ib, wc, r, blockIdx.x, nbig);
-  else kp_small_body(d, ib, wc, r, nb, blockIdx.x - nbig, gridDim.x - nbig);
+  else kp_small_body(d, ib, wc, r, nb, blockIdx.x - nbig, gridDim.x - nbig, w0);
 }
 
 // ---- inboxes longer than one wave: sorted into canonical (sender, seq) order = ascending outbox
@@ -861,17 +871,21 @@ __device__ __attribute__((always_inline)) inline void sort_body(const Dev& d, co
 // Ack :418-447, maybe_sync :707-740).
 constexpr uint32_t FAST_MAX = 8;
 __device__ __attribute__((always_inline)) inline void fast_body(const Dev& d, const OutBuf& ib, const OutBuf& ob, const WaveCtl& wc,
-                                                               int32_t r, uint32_t* slow, uint32_t bid) {
+                                                               int32_t r, uint32_t* slow, uint32_t bid, uint32_t* defer,
+                                                               uint32_t* w0) {
   const uint32_t nact = d.ctr[C_ACTIVE];
   const uint32_t it = bid * blockDim.x + threadIdx.x;
   const uint8_t now = enc(r, r);
   unsigned long long curovf = 0, over = 0;
-  bool to_slow = false;
+  bool to_slow = false, held = false;
   uint32_t i = 0;
   if (it < nact) {
     i = wc.active[it];
     const uint32_t icnt = wc.cnt1[i];
-    bool fast = icnt && icnt <= FAST_MAX && !d.dirty[i];
+    // split wave 0: a BIG group's destination (k_kp's own test) belongs to its group on the side stream until
+    // the join: nothing of its row is read here, and its counters stay for the deferred k_proc pass
+    held = defer && wc.kcnt[i] && wc.kpay[i] >= ((d.dbg & KB_DBG_KP_BIG_SMALL) ? 0u : KP_BIG);
+    bool fast = !held && icnt && icnt <= FAST_MAX && !d.dirty[i];
     uint32_t g[FAST_MAX];
     // Everything the handlers read is loaded up front, each group of loads in flight together: the
     // records (kept in registers), the senders' member words and stamps (a handler changes only its own
@@ -908,7 +922,7 @@ __device__ __attribute__((always_inline)) inline void fast_body(const Dev& d, co
         }
       }
     }
-    to_slow = icnt && !fast;
+    to_slow = !held && icnt && !fast;
     if (to_slow && (d.dev & 256)) {                   // why nodes go to k_proc (KB_DEV=256, KB_DEBUG_WAVES)
       bool kpr = false, nonmem = false;
       if (icnt <= FAST_MAX) {
@@ -996,8 +1010,9 @@ __device__ __attribute__((always_inline)) inline void fast_body(const Dev& d, co
       ob.cnt[i] = oseq;
       d.flog_n[i] = fn;
     }
-    if (!to_slow) wave_ctr_clear(wc, i);              // done with this node for the wave
+    if (!to_slow && !held) wave_ctr_clear(wc, i);     // done with this node for the wave
   }
+  if (held) defer[atomicAdd(&w0[W0_DEFER], 1u)] = i;   // a few dozen a round: one atomic each
   // the rest goes to k_proc: listed with one atomic per workgroup (the list counter is one word)
   __shared__ uint32_t s_wn[16], s_wb[16];
   const unsigned long long sm = __ballot(to_slow);
@@ -1026,25 +1041,32 @@ __device__ __attribute__((always_inline)) inline void fast_body(const Dev& d, co
 // 256-thread workgroups: the fast lane's nodes are then spread over every CU (with 1024-thread workgroups the
 // (R + 1023) / 1024 fast workgroups, one per CU at this kernel's occupancy, left most CUs idle)
 constexpr uint32_t SORTFAST_T = 256;
+// (defer, w0: split wave 0's deferred list and counters; null in every other launch)
 __global__ __launch_bounds__(SORTFAST_T) void k_sortfast(Dev d, OutBuf ib, OutBuf ob, WaveCtl wc, int32_t r_arg, uint32_t* slow,
-                                                   uint32_t nsort) {
+                                                   uint32_t nsort, uint32_t* defer, uint32_t* w0) {
   const int32_t r = round_of(d, r_arg);
   if (blockIdx.x < nsort) sort_body(d, wc, r, blockIdx.x, nsort);
-  else fast_body(d, ib, ob, wc, r, slow, blockIdx.x - nsort);
+  else fast_body(d, ib, ob, wc, r, slow, blockIdx.x - nsort, defer, w0);
 }
 
 constexpr uint32_t KB_KPR_BATCH = 4;        // KPR reply scan: 64-entry log batches in flight per step
 constexpr uint32_t KB_PROC_MANY = 1;        // batches of >= 8 prologue insertions fold one per lane (0: the whole wave on each)
 constexpr uint32_t KB_PROC_WPE = 1;         // minimum waves per SIMD k_proc is compiled for (1 = the compiler's choice)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KB_PROC_WPE)))
-void k_proc(Dev d, OutBuf ib, OutBuf ob, WaveCtl wc, int32_t r_arg, const uint32_t* list) {
+void k_proc(Dev d, OutBuf ib, OutBuf ob, WaveCtl wc, int32_t r_arg, const uint32_t* list, const uint32_t* count,
+            uint32_t* ticket) {
   const int32_t r = round_of(d, r_arg);
   __shared__ uint32_t ztab[ZT * 128];
   __shared__ Susp s_susp[4][SLOTS];
   __shared__ Cur s_cur[4][CSLOTS];
   __shared__ uint2 s_suf[4][NSEG + 1];
-  const uint32_t nact = d.ctr[C_SLOW];                // the nodes k_proc_fast left (list)
+  // list / count: the nodes k_sortfast left (slow, C_SLOW), or split wave 0's deferred nodes after the join.
+  // ticket (split wave 0's main launch): the waves draw their nodes from a counter instead of striding, because
+  // the workgroups that find their CU held by a BIG KnownPeers group start only when it ends, and a fixed share
+  // would then finish a whole launch after the others
+  const uint32_t nact = *count;
   if (blockIdx.x * 4 >= nact) return;                 // no node for this workgroup (before the table load)
+  const bool deferred = count != d.ctr + C_SLOW;
   load_ztab(d, ztab);
   const uint32_t wv = threadIdx.x >> 6;
   const uint32_t l = lane();
@@ -1056,8 +1078,20 @@ void k_proc(Dev d, OutBuf ib, OutBuf ob, WaveCtl wc, int32_t r_arg, const uint32
   // stamps / log entries / bits written, checkpoints and the member bytes + table words of every
   // (partial) fold, freshness-log entries scanned, records and payload ids emitted
   unsigned long long w_bytes = 0;
-  for (uint32_t it = blockIdx.x * 4 + wv; it < nact; it += gridDim.x * 4) {
+  // the first gridDim.x * 4 nodes go by position, the rest by ticket
+  auto next_it = [&](uint32_t it) __attribute__((always_inline)) -> uint32_t {
+    if (!ticket) return it + gridDim.x * 4;
+    uint32_t k = 0;
+    if (l == 0) k = atomicAdd(ticket, 1u);
+    return gridDim.x * 4 + rdl(k, 0);
+  };
+  for (uint32_t it = blockIdx.x * 4 + wv; it < nact; it = next_it(it)) {
     const uint32_t i = list[it];
+    if (deferred) {
+      // a BIG group's destination with no in-order delivery: only its counters are left to clear
+      if (!wc.cnt1[i]) { if (l == 0) wave_ctr_clear(wc, i); continue; }
+      if (l == 0) path_hit(d, PATH_PROC_DEFERRED);
+    }
     const bool tdbg = (d.dev & 64) != 0;                // timing breakdown (KB_DEV=64, KB_DEBUG_WAVES)
     const uint64_t t_node = tdbg ? wall_clock64() : 0;
     uint64_t t_base = 0, t_ins = 0;
