@@ -76,6 +76,51 @@ class KbKernelTime(C.Structure):
                 ("has_bytes", C.c_uint32), ("pad", C.c_uint32), ("wave_ms", C.c_double * KB_WAVE_SLOTS)]
 
 
+KB_CENSUS_NONE = 0xFFFFFFFF      # "no such id" in every census summary (the result modules import it from here)
+
+
+def _summary(st: C.Structure, lists=()) -> dict:
+    """A census summary struct as a dict in field order: ints, and lists of ints for the array fields in `lists`."""
+    return {n: [int(x) for x in getattr(st, n)] if n in lists else int(getattr(st, n))
+            for n, _ in st._fields_ if n not in ("reserved", "pad")}
+
+
+def diff_results(a, b, array_names) -> list[str]:
+    """What differs between two census results: the summary fields first, then each named array (None on both sides
+    is equal).  A per-id array reports how many entries differ and the first; a list ([n, k] rows) or arrays of
+    different lengths their lengths."""
+    import numpy as np
+    out = [f"summary.{k}: {v} != {b.summary[k]}" for k, v in a.summary.items() if b.summary[k] != v]
+    for name in array_names:
+        x, y = getattr(a, name), getattr(b, name)
+        if (x is None) != (y is None):
+            out.append(f"{name}: only one side has the array")
+        elif x is not None and not np.array_equal(x, y):
+            if x.ndim > 1 or x.shape != y.shape:
+                out.append(f"{name}: {len(x)} listed != {len(y)} listed, or other entries")
+            else:
+                bad = np.flatnonzero(x != y)
+                out.append(f"{name}: {len(bad)} differ, first id {bad[0]}: {x[bad[0]]} != {y[bad[0]]}")
+    return out
+
+
+_PTR = {"u4": C.POINTER(C.c_uint32), "i4": C.POINTER(C.c_int32), "u8": C.POINTER(C.c_uint64)}
+
+
+def _out_arrays(arrays: bool, *groups):
+    """The output arrays of a census call.  A group is ([dtype, ...], n): arrays of n entries that share one capacity
+    argument.  Returns the numpy arrays, flat, and the call's arguments (each group's pointers, then its capacity);
+    with arrays=False a None per array, NULL pointers and zero capacities."""
+    import numpy as np
+    outs, args = [], []
+    for dtypes, n in groups:
+        made = [np.zeros(n, dtype=dt) if arrays else None for dt in dtypes]
+        outs += made
+        args += [m.ctypes.data_as(_PTR[dt]) if arrays else None for m, dt in zip(made, dtypes)]
+        args.append(n if arrays else 0)
+    return outs, args
+
+
 class KbCensus(C.Structure):
     """kb_census (include/kaboodle_census.h)."""
     _fields_ = [("round", C.c_int32), ("observers", C.c_uint32), ("running", C.c_uint32), ("exact_views", C.c_uint32),
@@ -85,10 +130,7 @@ class KbCensus(C.Structure):
                 ("reserved", C.c_uint64 * 4)]
 
     def as_dict(self) -> dict:
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
-
-
-KB_CENSUS_NONE = 0xFFFFFFFF
+        return _summary(self)
 
 
 class KbReciprocity(C.Structure):
@@ -99,7 +141,7 @@ class KbReciprocity(C.Structure):
                 ("reserved", C.c_uint64 * 4)]
 
     def as_dict(self) -> dict:
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+        return _summary(self)
 
 
 class KbFpClass(C.Structure):
@@ -115,8 +157,8 @@ class KbFpClasses(C.Structure):
                 ("listed_observers", C.c_uint32), ("reserved", C.c_uint64 * 4)]
 
     def as_dict(self) -> dict:
-        d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n not in ("reserved", "size_hist")}
-        d["size_hist"] = [int(x) for x in self.size_hist]
+        d = _summary(self, ("size_hist",))
+        d["size_hist"] = d.pop("size_hist")              # after listed and listed_observers
         return d
 
 
@@ -132,10 +174,7 @@ class KbLatCensus(C.Structure):
                 ("hist", C.c_uint64 * 17), ("orphans", C.c_uint64), ("reserved", C.c_uint64 * 4)]
 
     def as_dict(self) -> dict:
-        d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n not in ("reserved", "hist")}
-        d["hist"] = [int(x) for x in self.hist]
-        return {k: d[k] for k in ("round", "observers", "measured", "sum_ms", "min_ms", "max_ms", "max_peer",
-                                  "measured_ids", "hist", "orphans")}
+        return _summary(self, ("hist",))
 
 
 _LATC_OUT = [C.POINTER(KbLatCensus), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
@@ -151,9 +190,7 @@ class KbAgeCensus(C.Structure):
                 ("pad", C.c_uint32), ("hist", C.c_uint64 * 256), ("reserved", C.c_uint64 * 4)]
 
     def as_dict(self) -> dict:
-        d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n not in ("reserved", "hist", "pad")}
-        d["hist"] = [int(x) for x in self.hist]
-        return d
+        return _summary(self, ("hist",))
 
 
 _AGEC_OUT = [C.POINTER(KbAgeCensus), *[C.POINTER(C.c_uint32)] * 4, C.POINTER(C.c_int32), C.c_size_t,
@@ -416,12 +453,10 @@ def _fp_classes_call(lib: SimLib, name: str, head: tuple, top: int, arrays: bool
     from .classes import FpClasses
     out, got = KbFpClasses(), C.c_size_t(0)
     lst = (KbFpClass * max(top, 1))()
-    rep = np.zeros(n, dtype=np.uint32) if arrays else None
-    size = np.zeros(n, dtype=np.uint32) if arrays else None
-    ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32)) if a is not None else None
-    lib.call(name, *head, C.byref(out), lst if top else None, top, C.byref(got), ptr(rep), ptr(size), n if arrays else 0)
+    outs, args = _out_arrays(arrays, (["u4", "u4"], n))
+    lib.call(name, *head, C.byref(out), lst if top else None, top, C.byref(got), *args)
     cls = np.array([(e.fp, e.size, e.rep) for e in lst[: got.value]], dtype=np.uint32).reshape(-1, 3)
-    return FpClasses(out.as_dict(), cls, rep, size)
+    return FpClasses(out.as_dict(), cls, *outs)
 
 
 def fp_classes_of(lib: SimLib, fps, running, true_fp: int, top: int = 16, arrays: bool = True, device: int = 0):
@@ -440,18 +475,11 @@ def fp_classes_of(lib: SimLib, fps, running, true_fp: int, top: int = 16, arrays
 def _latency_census_call(lib: SimLib, name: str, head: tuple, arrays: bool, n_ids: int, n_rows: int):
     """kb_sim_latency_census / kb_latency_census_of with the outputs of Sim.latency_census: with arrays, the four
     arrays over `n_ids` ids and the two over `n_rows` rows."""
-    import numpy as np
     from .latency import LatencyCensus
     out = KbLatCensus()
-    if not arrays:
-        lib.call(name, *head, C.byref(out), None, None, None, None, 0, None, None, 0)
-        return LatencyCensus(out.as_dict())
-    mb, mn, mx = (np.zeros(n_ids, dtype=np.uint32) for _ in range(3))
-    sm, rc, rs = np.zeros(n_ids, dtype=np.uint64), np.zeros(n_rows, dtype=np.uint32), np.zeros(n_rows, dtype=np.uint64)
-    p32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
-    p64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
-    lib.call(name, *head, C.byref(out), p32(mb), p64(sm), p32(mn), p32(mx), n_ids, p32(rc), p64(rs), n_rows)
-    return LatencyCensus(out.as_dict(), mb, sm, mn, mx, rc, rs)
+    outs, args = _out_arrays(arrays, (["u4", "u8", "u4", "u4"], n_ids), (["u4", "u8"], n_rows))
+    lib.call(name, *head, C.byref(out), *args)
+    return LatencyCensus(out.as_dict(), *outs)
 
 
 def latency_census_of(lib: SimLib, lat, member, running, arrays: bool = True, device: int = 0):
@@ -471,18 +499,11 @@ def latency_census_of(lib: SimLib, lat, member, running, arrays: bool = True, de
 def _age_census_call(lib: SimLib, name: str, head: tuple, arrays: bool, n_ids: int, n_rows: int):
     """kb_sim_age_census with the outputs of Sim.age_census: with arrays, the five arrays over
     `n_ids` ids and the four over `n_rows` rows."""
-    import numpy as np
     from .age import AgeCensus
     out = KbAgeCensus()
-    if not arrays:
-        lib.call(name, *head, C.byref(out), None, None, None, None, None, 0, None, None, None, None, 0)
-        return AgeCensus(out.as_dict())
-    by = [np.zeros(n_ids, dtype=np.uint32) for _ in range(4)]
-    lh = np.zeros(n_ids, dtype=np.int32)
-    rw = [np.zeros(n_rows, dtype=np.uint32) for _ in range(4)]
-    p32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
-    lib.call(name, *head, C.byref(out), *map(p32, by), lh.ctypes.data_as(C.POINTER(C.c_int32)), n_ids, *map(p32, rw), n_rows)
-    return AgeCensus(out.as_dict(), *by, lh, *rw)
+    outs, args = _out_arrays(arrays, (["u4"] * 4 + ["i4"], n_ids), (["u4"] * 4, n_rows))
+    lib.call(name, *head, C.byref(out), *args)
+    return AgeCensus(out.as_dict(), *outs)
 
 
 class Sim:
@@ -691,21 +712,20 @@ class Sim:
         from .census import Census, census_ref
         if "sim_census" not in self.lib.fn:
             return census_ref(self)
-        import numpy as np
         out = KbCensus()
-        if not arrays:
-            self.lib.call("sim_census", self.h, C.byref(out), None, 0, None, None, 0)
-            return Census(out.as_dict(), None, None, None)
-        kb, mi, st = (np.zeros(self.capacity, dtype=np.uint32) for _ in range(3))
-        ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
-        self.lib.call("sim_census", self.h, C.byref(out), ptr(kb), self.capacity, ptr(mi), ptr(st), self.capacity)
-        return Census(out.as_dict(), kb, mi, st, self.scalars()[:, 0] != 0)
+        outs, args = _out_arrays(arrays, (["u4"], self.capacity), (["u4", "u4"], self.capacity))
+        self.lib.call("sim_census", self.h, C.byref(out), *args)
+        return Census(out.as_dict(), *outs, self.scalars()[:, 0] != 0 if arrays else None)
+
+    def _device_ms(self, name: str) -> float:
+        """Device time in ms of the last call of census `name` on this handle (kb_sim_<name>_device_ms)."""
+        v = C.c_double(0)
+        self.lib.call(f"sim_{name}_device_ms", self.h, C.byref(v))
+        return v.value
 
     def census_device_ms(self) -> float:
         """Device time of the last census() in ms (kb_sim_census_device_ms; HIP library only)."""
-        v = C.c_double()
-        self.lib.call("sim_census_device_ms", self.h, C.byref(v))
-        return v.value
+        return self._device_ms("census")
 
     def reciprocity(self, arrays: bool = True, max_pairs: int = 65536):
         """The reciprocity census (include/kaboodle_reciprocity.h): a `Reciprocity` with `summary` (dict of
@@ -719,21 +739,15 @@ class Sim:
             return reciprocity_ref(self, max_pairs, arrays)
         import numpy as np
         out = KbReciprocity()
-        if not arrays:
-            self.lib.call("sim_reciprocity", self.h, C.byref(out), None, None, None, 0, None, 0)
-            return Reciprocity(out.as_dict(), None, None, None, None)
-        mu, lk, lb = (np.zeros(self.capacity, dtype=np.uint32) for _ in range(3))
-        pairs = np.zeros((max(max_pairs, 1), 2), dtype=np.uint32)
-        ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
-        self.lib.call("sim_reciprocity", self.h, C.byref(out), ptr(mu), ptr(lk), ptr(lb), self.capacity, ptr(pairs),
-                      max_pairs)
-        return Reciprocity(out.as_dict(), mu, lk, lb, pairs[: out.pairs_listed].copy())
+        (mu, lk, lb), args = _out_arrays(arrays, (["u4"] * 3, self.capacity))
+        pairs = np.zeros((max(max_pairs, 1), 2), dtype=np.uint32) if arrays else None
+        self.lib.call("sim_reciprocity", self.h, C.byref(out), *args,
+                      pairs.ctypes.data_as(C.POINTER(C.c_uint32)) if arrays else None, max_pairs if arrays else 0)
+        return Reciprocity(out.as_dict(), mu, lk, lb, pairs[: out.pairs_listed].copy() if arrays else None)
 
     def reciprocity_device_ms(self) -> float:
         """Device time of the last reciprocity() in ms (kb_sim_reciprocity_device_ms; HIP library only)."""
-        v = C.c_double()
-        self.lib.call("sim_reciprocity_device_ms", self.h, C.byref(v))
-        return v.value
+        return self._device_ms("reciprocity")
 
     def fp_classes(self, top: int = 16, arrays: bool = True):
         """The fingerprint-class census (include/kaboodle_classes.h): an `FpClasses` with `summary` (dict of
@@ -748,9 +762,7 @@ class Sim:
 
     def fp_classes_device_ms(self) -> float:
         """Device time of the last fp_classes() in ms (kb_sim_fp_classes_device_ms; HIP library only)."""
-        v = C.c_double()
-        self.lib.call("sim_fp_classes_device_ms", self.h, C.byref(v))
-        return v.value
+        return self._device_ms("fp_classes")
 
     def latency_census(self, arrays: bool = True):
         """The latency census (include/kaboodle_latency.h): a `LatencyCensus` with `summary` (dict of
@@ -762,6 +774,10 @@ class Sim:
             from .latency import latency_census_ref
             return latency_census_ref(self, arrays)
         return _latency_census_call(self.lib, "sim_latency_census", (self.h,), arrays, self.capacity, self.capacity)
+
+    def latency_census_device_ms(self) -> float:
+        """Device time of the last latency_census() in ms (kb_sim_latency_census_device_ms; HIP library only)."""
+        return self._device_ms("latency_census")
 
     def age_census(self, arrays: bool = True):
         """The contact-age census (include/kaboodle_age.h): an `AgeCensus` with `summary` (dict of kb_age_census)
@@ -776,9 +792,7 @@ class Sim:
 
     def age_census_device_ms(self) -> float:
         """Device time of the last age_census() in ms (kb_sim_age_census_device_ms; HIP library only)."""
-        v = C.c_double(0)
-        self.lib.call("sim_age_census_device_ms", self.h, C.byref(v))
-        return v.value
+        return self._device_ms("age_census")
 
     def snapshot(self) -> bytes:
         """The mesh's state after the last completed round as one byte string (kb_sim_snapshot,
@@ -811,15 +825,7 @@ class Sim:
     def snapshot_device_ms(self) -> float:
         """Device time of the last snapshot()'s pack, or of the restore that made this handle, in ms
         (kb_sim_snapshot_device_ms)."""
-        v = C.c_double(0)
-        self.lib.call("sim_snapshot_device_ms", self.h, C.byref(v))
-        return v.value
-
-    def latency_census_device_ms(self) -> float:
-        """Device time of the last latency_census() in ms (kb_sim_latency_census_device_ms; HIP library only)."""
-        v = C.c_double()
-        self.lib.call("sim_latency_census_device_ms", self.h, C.byref(v))
-        return v.value
+        return self._device_ms("snapshot")
 
     def row(self, node: int):
         import numpy as np

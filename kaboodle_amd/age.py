@@ -13,7 +13,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-KB_CENSUS_NONE = 0xFFFFFFFF
+from ._ffi import KB_CENSUS_NONE, diff_results
+
 KB_AGE_HIST = 256
 INT32_MIN = -(2 ** 31)
 SHARE_AGE = 10                    # src/kaboodle.rs:49: a KnownPeersRequest reply lists entries stamped within it
@@ -45,16 +46,7 @@ class AgeCensus:
 
     def same_as(self, other: "AgeCensus") -> list[str]:
         """The differences to another contact-age census (empty: identical summary and arrays)."""
-        out = [f"summary.{k}: {v} != {other.summary[k]}" for k, v in self.summary.items() if other.summary[k] != v]
-        for name in ARRAYS:
-            a, b = getattr(self, name), getattr(other, name)
-            if (a is None) != (b is None):
-                out.append(f"{name}: only one side has the array")
-            elif a is not None and not np.array_equal(a, b):
-                bad = np.flatnonzero(a != b) if a.shape == b.shape else [0]
-                out.append(f"{name}: {len(bad)} differ, first id {bad[0]}" +
-                           (f": {a[bad[0]]} != {b[bad[0]]}" if a.shape == b.shape else " (shapes)"))
-        return out
+        return diff_results(self, other, ARRAYS)
 
 
 def last_round(round_: int) -> int:

@@ -12,7 +12,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-KB_CENSUS_NONE = 0xFFFFFFFF
+from ._ffi import KB_CENSUS_NONE, diff_results
+
 SUMMARY_FIELDS = ("round", "observers", "running", "exact_views", "pairs", "missing", "stale", "full_ids",
                   "ghost_ids", "least_known", "least_known_by", "top_ghost", "top_ghost_by")
 
@@ -31,13 +32,7 @@ class Census:
 
     def same_as(self, other: "Census") -> list[str]:
         """The differences to another census (empty: identical summary and arrays)."""
-        out = [f"summary.{k}: {v} != {other.summary[k]}" for k, v in self.summary.items() if other.summary[k] != v]
-        for name in ("known_by", "missing", "stale"):
-            a, b = getattr(self, name), getattr(other, name)
-            if not np.array_equal(a, b):
-                bad = np.flatnonzero(a != b)
-                out.append(f"{name}: {len(bad)} differ, first id {bad[0]}: {a[bad[0]]} != {b[bad[0]]}")
-        return out
+        return diff_results(self, other, ("known_by", "missing", "stale"))
 
 
 def summarize(round_: int, running: np.ndarray, external: np.ndarray, held: np.ndarray, known_by: np.ndarray,

@@ -12,7 +12,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-KB_CENSUS_NONE = 0xFFFFFFFF
+from ._ffi import KB_CENSUS_NONE, diff_results
+
 KB_FPC_LIST_MAX = 1024
 SUMMARY_FIELDS = ("round", "observers", "classes", "largest", "singletons", "true_fp", "true_size", "true_rank",
                   "size_hist", "listed", "listed_observers")
@@ -31,19 +32,7 @@ class FpClasses:
 
     def same_as(self, other: "FpClasses") -> list[str]:
         """The differences to another class census (empty: identical summary, list and arrays)."""
-        out = [f"summary.{k}: {v} != {other.summary[k]}" for k, v in self.summary.items() if other.summary[k] != v]
-        if not np.array_equal(self.classes, other.classes):
-            out.append(f"classes: {self.classes[:4].tolist()}... ({len(self.classes)}) != "
-                       f"{other.classes[:4].tolist()}... ({len(other.classes)})")
-        for name in ("rep", "size"):
-            a, b = getattr(self, name), getattr(other, name)
-            if (a is None) != (b is None):
-                out.append(f"{name}: only one side has the array")
-            elif a is not None and not np.array_equal(a, b):
-                bad = np.flatnonzero(a != b) if a.shape == b.shape else [0]
-                out.append(f"{name}: {len(bad)} differ, first id {bad[0]}" +
-                           (f": {a[bad[0]]} != {b[bad[0]]}" if a.shape == b.shape else " (shapes)"))
-        return out
+        return diff_results(self, other, ("classes", "rep", "size"))
 
 
 def fp_classes_of_arrays(fps, running, true_fp: int, top: int = 16, arrays: bool = True, round_: int = -1) -> FpClasses:

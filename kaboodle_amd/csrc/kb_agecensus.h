@@ -1,11 +1,11 @@
 // kb_agecensus.h — the contact-age census (include/kaboodle_age.h): per id how many observers hold
 // it as suspect, ancient, windowed and fresh and the latest instant any of them heard from it; per row the same four
 // counts over its view; a histogram of the windowed cells by age.  Included at the end of kb_sim.hip; reads the
-// sparse engine's state, writes only its own scratch.  Dense handles refuse (§17: their pass is left out).
+// sparse engine's state, writes only its own scratch.  Dense handles are refused (§17: their pass is left out).
 //
 // Sparse rows: a thread per row over its entry list, the shape of k_cs_sp_rows.  Explicit entries carry the stamp,
 // so suspect, windowed and fresh cells are the entries with a nonzero stamp that are members; the ancient counts
-// follow from the view census's sparse pass (cs_sparse_pass, reused): ancient = |view| - [self] - suspects - windowed.
+// follow from the view census's sparse pass (cs_leaf(SpSim*), reused): ancient = |view| - [self] - suspects - windowed.
 // The histogram (windowed cells by stamp byte; the host turns bytes into ages) goes through a workgroup's LDS words.
 #pragma once
 #include "../../include/kaboodle_age.h"
@@ -125,32 +125,17 @@ static int ag_summary(const AgPart& p, int32_t round, kb_age_census* out, int32_
   out->cells = out->suspects + out->ancient + out->windowed;
   return KB_OK;
 }
-static void ag_deliver(const AgPart& p, uint32_t* sb, uint32_t* ab, uint32_t* wb, uint32_t* fb, uint32_t* rs, uint32_t* ra,
-                       uint32_t* rw, uint32_t* rf) {
-  if (sb) memcpy(sb, p.sb.data(), 4 * p.sb.size());
-  if (ab) memcpy(ab, p.ab.data(), 4 * p.ab.size());
-  if (wb) memcpy(wb, p.wb.data(), 4 * p.wb.size());
-  if (fb) memcpy(fb, p.fb.data(), 4 * p.fb.size());
-  if (rs) memcpy(rs, p.rs.data(), 4 * p.rs.size());
-  if (ra) memcpy(ra, p.ra.data(), 4 * p.ra.size());
-  if (rw) memcpy(rw, p.rw.data(), 4 * p.rw.size());
-  if (rf) memcpy(rf, p.rf.data(), 4 * p.rf.size());
-}
 
 // one leaf's pass (route() hands every shard of a group here in turn)
-static int ag_leaf(kb_sim*, AgPart&) {
-  seterr("kb_sim_age_census: dense rows are not answered yet (KB_VARIANT_SPARSE_ROWS handles are)");
-  return KB_INVALID_OPERATION;
-}
+static int ag_leaf(kb_sim*, AgPart&) { return KB_INVALID_OPERATION; }   // not reached: census_gate refuses dense rows
 static int ag_leaf(SpSim* S, AgPart& p) {
   (void)hipSetDevice(S->device);
   const SpDev& d = S->d;
   const uint32_t C = S->C, R = S->R;
-  // |view| and known_by of this shard's rows: the view census's sparse pass
+  // |view| and known_by of this shard's rows: the view census's sparse pass (it uses that census's scratch, cs_buf)
   CsPart cp;
   cs_part_init(cp, C);
-  double cs_ms = 0;                                               // (the pass reuses the view census's scratch, cs_buf)
-  { const int rc = cs_sparse_pass(S, cp, &cs_ms); if (rc) return rc; }
+  { const int rc = cs_leaf(S, cp); if (rc) return rc; }
   const size_t words = 512ull + 4ull * C + 4ull * R;
   if (!S->ag_buf) {
     if (sp_alloc(S, &S->ag_buf, words) != hipSuccess) { seterr("age census: device allocation failed"); return KB_CAPACITY; }
@@ -164,13 +149,13 @@ static int ag_leaf(SpSim* S, AgPart& p) {
   kb::k_age_sp_rows<<<(R + 255) / 256, 256, 0, S->st>>>(d, a);
   tm.stop(S->st);
   HIPCHK(hipGetLastError());
-  std::vector<uint32_t> by(4ull * C), rowc(4ull * R);
+  std::vector<uint32_t> by, rowc;
   unsigned long long hist[256];
   HIPCHK(hipMemcpyAsync(hist, a.hist, sizeof hist, hipMemcpyDeviceToHost, S->st));
-  HIPCHK(hipMemcpyAsync(by.data(), a.by, 16ull * C, hipMemcpyDeviceToHost, S->st));
-  HIPCHK(hipMemcpyAsync(rowc.data(), a.rowc, 16ull * R, hipMemcpyDeviceToHost, S->st));
+  HIPCHK(fetch(by, a.by, 4ull * C, S->st));
+  HIPCHK(fetch(rowc, a.rowc, 4ull * R, S->st));
   HIPCHK(hipStreamSynchronize(S->st));
-  S->ag_ms = cs_ms + tm.ms(); p.ms += S->ag_ms;
+  p.ms += cp.ms + tm.ms();
   p.alive = cp.alive; p.ext = cp.ext;
   for (uint32_t k = 0; k < 256; ++k) p.hist[k] += hist[k];
   // ancient_by = known_by - [self] - suspected_by - windowed_by, over this shard's rows (sums of shards add up)
@@ -191,45 +176,24 @@ static int ag_leaf(SpSim* S, AgPart& p) {
   return KB_OK;
 }
 
-static int ag_check(const void* out, const void* ids_any, size_t cap_ids, size_t n_ids, const void* rows_any, size_t cap_rows,
-                    size_t n_rows, const char* who) {
-  if (!out) return KB_INVALID_ARGUMENT;
-  if ((ids_any && cap_ids < n_ids) || (rows_any && cap_rows < n_rows)) {
-    seterr(std::string(who) + ": an output array is shorter than the capacity"); return KB_INVALID_ARGUMENT;
-  }
-  return KB_OK;
-}
-#define AG_ANY_IDS (suspected_by ? (const void*)suspected_by : ancient_by ? (const void*)ancient_by : windowed_by ? (const void*)windowed_by : \
-                    fresh_by ? (const void*)fresh_by : (const void*)last_heard)
-#define AG_ANY_ROWS (suspects ? (const void*)suspects : ancient ? (const void*)ancient : windowed ? (const void*)windowed : (const void*)fresh)
-
 extern "C" int kb_sim_age_census(kb_sim* s, kb_age_census* out, uint32_t* suspected_by, uint32_t* ancient_by, uint32_t* windowed_by,
                                  uint32_t* fresh_by, int32_t* last_heard, size_t cap_ids, uint32_t* suspects, uint32_t* ancient,
                                  uint32_t* windowed, uint32_t* fresh, size_t cap_rows) {
   if (!s) return KB_INVALID_ARGUMENT;
-  { const int rc = ag_check(out, AG_ANY_IDS, cap_ids, s->C, AG_ANY_ROWS, cap_rows, s->C, "kb_sim_age_census"); if (rc) return rc; }
-  const Kind kd = kind_of(s);
-  if (kd.rank) {
-    seterr("kb_sim_age_census: a rank handle holds its own rows only (use kb_sim_create or kb_sim_create_local)");
-    return KB_INVALID_OPERATION;
-  }
-  if (!kd.sparse) { AgPart none; return ag_leaf(s, none); }
+  { const int rc = census_caps("kb_sim_age_census", out, any_of(suspected_by, ancient_by, windowed_by, fresh_by, last_heard), cap_ids, s->C,
+                               any_of(suspects, ancient, windowed, fresh), cap_rows, s->C); if (rc) return rc; }
+  { const int rc = census_gate(s, "kb_sim_age_census", {"", nullptr, "are not answered yet (KB_VARIANT_SPARSE_ROWS handles are)"});
+    if (rc) return rc; }
   AgPart p;
   ag_part_init(p, s->C, s->C);
   int32_t round = 0;
   { const int rc = route(s, R_ALL, 0, [&](auto* e) { return ag_leaf(e, p); }); if (rc) return rc; }
   { const int rc = route(s, R_FIRST, 0, [&](auto* e) { round = e->round; return KB_OK; }); if (rc) return rc; }
-  s->ag_ms = p.ms;
+  s->census_ms[CM_AGE] = p.ms;
   { const int rc = ag_summary(p, round, out, last_heard, "kb_sim_age_census"); if (rc) return rc; }
-  ag_deliver(p, suspected_by, ancient_by, windowed_by, fresh_by, suspects, ancient, windowed, fresh);
+  deliver(suspected_by, p.sb); deliver(ancient_by, p.ab); deliver(windowed_by, p.wb); deliver(fresh_by, p.fb);
+  deliver(suspects, p.rs); deliver(ancient, p.ra); deliver(windowed, p.rw); deliver(fresh, p.rf);
   return KB_OK;
 }
 
-extern "C" int kb_sim_age_census_device_ms(kb_sim* s, double* ms) {
-  if (!s || !ms) return KB_INVALID_ARGUMENT;
-  *ms = s->ag_ms;
-  return KB_OK;
-}
-
-#undef AG_ANY_IDS
-#undef AG_ANY_ROWS
+extern "C" int kb_sim_age_census_device_ms(kb_sim* s, double* ms) { return census_ms_get(s, CM_AGE, ms); }

@@ -1,6 +1,7 @@
 // kb_census.h — the view census (include/kaboodle_census.h): for every id the number of running
 // rows whose view holds it, and for every running row how far its view is from the running set.  Included at
-// the end of kb_sim.hip; reads the engines' state, writes only its own scratch.
+// the end of kb_sim.hip; reads the engines' state, writes only its own scratch.  The host side stands on the
+// frame of kb_censusframe.h: cs_leaf(kb_sim*) / cs_leaf(SpSim*) are the leaves that route() hands the shards to.
 //
 // Dense engine: one streaming pass over the member bits (Dev::bits, [rows][W/32]).  A lane owns one 16-byte
 // column group (4 words = 128 ids) and walks down a tile of rows, so each row read is 1 KiB contiguous per
@@ -222,22 +223,16 @@ struct CsPart {
 static void cs_part_init(CsPart& p, uint32_t C) {
   p.kb.assign(C, 0); p.view.assign(C, 0); p.run.assign(C, 0); p.stale.assign(C, 0); p.held.assign(C, 0);
 }
-struct CsTimer {
-  hipEvent_t a = nullptr, b = nullptr;
-  bool start(hipStream_t st) { return hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess && hipEventRecord(a, st) == hipSuccess; }
-  void stop(hipStream_t st) { (void)hipEventRecord(b, st); }
-  double ms() { float t = 0; if (a && b && hipEventElapsedTime(&t, a, b) != hipSuccess) t = 0; return t; }
-  ~CsTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
 // the rows' counts of a shard (device [3][R]) and its known_by land in the part, added to what is there
 static int cs_collect(CsPart& p, uint32_t C, uint32_t lo, uint32_t R, const uint32_t* d_kb, const uint32_t* d_rowc,
                       const uint8_t* d_alive, const uint8_t* d_ext, hipStream_t st) {
+  // sized before the first copy waits for the kernels: zero-filling [C] and [3][R] words overlaps their run
   std::vector<uint32_t> kb(C), rc(3ull * R);
   p.alive.resize(C); p.ext.resize(C);
-  HIPCHK(hipMemcpyAsync(kb.data(), d_kb, 4ull * C, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(rc.data(), d_rowc, 12ull * R, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(p.alive.data(), d_alive, C, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(p.ext.data(), d_ext, C, hipMemcpyDeviceToHost, st));
+  HIPCHK(fetch(kb, d_kb, C, st));
+  HIPCHK(fetch(rc, d_rowc, 3ull * R, st));
+  HIPCHK(fetch(p.alive, d_alive, C, st));
+  HIPCHK(fetch(p.ext, d_ext, C, st));
   HIPCHK(hipStreamSynchronize(st));
   for (uint32_t j = 0; j < C; ++j) p.kb[j] += kb[j];
   for (uint32_t k = 0; k < R; ++k) {
@@ -246,7 +241,8 @@ static int cs_collect(CsPart& p, uint32_t C, uint32_t lo, uint32_t R, const uint
   return KB_OK;
 }
 
-static int cs_dense(kb_sim* s, CsPart& p) {
+// one leaf's pass (route() hands every shard of a group here in turn): dense rows
+static int cs_leaf(kb_sim* s, CsPart& p) {
   (void)hipSetDevice(s->device);
   const Dev& d = s->d;
   if (!s->cs_buf) HIPCHK(talloc(s, &s->cs_buf, (size_t)s->W + 3ull * s->R + 3ull * d.NWR));
@@ -271,13 +267,11 @@ static int cs_dense(kb_sim* s, CsPart& p) {
   HIPCHK(hipGetLastError());
   const int rc = cs_collect(p, s->C, s->lo, s->R, a.kb, a.rowc, d.alive, d.ext, s->st);
   if (rc) return rc;
-  s->cs_ms = tm.ms(); p.ms += s->cs_ms;
+  p.ms += tm.ms();
   return KB_OK;
 }
-
-// the sparse pass; its device time goes to *ms and the handle's own figure is left alone (the contact-age census
-// reuses the pass, kb_agecensus.h)
-static int cs_sparse_pass(SpSim* S, CsPart& p, double* ms) {
+// sparse rows (the contact-age census reuses the pass and its scratch, kb_agecensus.h)
+static int cs_leaf(SpSim* S, CsPart& p) {
   (void)hipSetDevice(S->device);
   const SpDev& d = S->d;
   const uint32_t C = S->C, R = S->R;
@@ -296,10 +290,9 @@ static int cs_sparse_pass(SpSim* S, CsPart& p, double* ms) {
   HIPCHK(hipGetLastError());
   const int rc = cs_collect(p, C, S->lo, R, a.kb, a.rowc, d.alive, d.ext, S->st);
   if (rc) return rc;
-  *ms = tm.ms(); p.ms += *ms;
+  p.ms += tm.ms();
   return KB_OK;
 }
-static int cs_sparse(SpSim* S, CsPart& p) { return cs_sparse_pass(S, p, &S->cs_ms); }
 
 // the O(ids) reductions of the summary, on the host
 static void cs_summary(const CsPart& p, uint32_t C, int32_t round, kb_census* out, uint32_t* missing, uint32_t* stale) {
@@ -332,29 +325,17 @@ static void cs_summary(const CsPart& p, uint32_t C, int32_t round, kb_census* ou
 
 extern "C" int kb_sim_census(kb_sim* s, kb_census* out, uint32_t* known_by, size_t cap_ids, uint32_t* missing,
                              uint32_t* stale, size_t cap_rows) {
-  if (!s || !out) return KB_INVALID_ARGUMENT;
-  if ((known_by && cap_ids < s->C) || ((missing || stale) && cap_rows < s->C)) {
-    seterr("kb_sim_census: an output array is shorter than the capacity"); return KB_INVALID_ARGUMENT;
-  }
+  if (!s) return KB_INVALID_ARGUMENT;
+  { const int rc = census_caps("kb_sim_census", out, known_by, cap_ids, s->C, any_of(missing, stale), cap_rows, s->C); if (rc) return rc; }
   CsPart p;
   cs_part_init(p, s->C);
   int32_t round = 0;
-  if (is_group(s)) {
-    for (kb_sim* t : s->shards) { const int rc = t->sp ? cs_sparse(t->sp, p) : cs_dense(t, p); if (rc) return rc; }
-    round = s->shards[0]->sp ? s->shards[0]->sp->round : s->shards[0]->round;
-  } else {
-    const int rc = s->sp ? cs_sparse(s->sp, p) : cs_dense(s, p);
-    if (rc) return rc;
-    round = s->sp ? s->sp->round : s->round;
-  }
-  s->cs_ms = p.ms;
+  { const int rc = route(s, R_ALL, 0, [&](auto* e) { return cs_leaf(e, p); }); if (rc) return rc; }
+  { const int rc = route(s, R_FIRST, 0, [&](auto* e) { round = e->round; return KB_OK; }); if (rc) return rc; }
+  s->census_ms[CM_VIEW] = p.ms;
   cs_summary(p, s->C, round, out, missing, stale);
-  if (known_by) memcpy(known_by, p.kb.data(), 4ull * s->C);
+  deliver(known_by, p.kb);
   return KB_OK;
 }
 
-extern "C" int kb_sim_census_device_ms(kb_sim* s, double* ms) {
-  if (!s || !ms) return KB_INVALID_ARGUMENT;
-  *ms = s->cs_ms;
-  return KB_OK;
-}
+extern "C" int kb_sim_census_device_ms(kb_sim* s, double* ms) { return census_ms_get(s, CM_VIEW, ms); }

@@ -279,15 +279,6 @@ static bool fc_plan(size_t n, FcPlan& p) {
 }
 static_assert(FA_WORDS * 4 <= 256 && sizeof(kb_fp_class) == 16, "kb_classes.h scratch layout");
 
-// the scratch grows, never shrinks; the previous call has synchronised its stream, so nothing uses the old one
-static int fc_reserve(void** buf, size_t* cap, size_t bytes) {
-  if (*buf && *cap >= bytes) return KB_OK;
-  if (*buf) { (void)hipFree(*buf); *buf = nullptr; *cap = 0; }
-  if (hipMalloc(buf, bytes) != hipSuccess) { *buf = nullptr; seterr("fp_classes: scratch allocation failed"); return KB_CAPACITY; }
-  *cap = bytes;
-  return KB_OK;
-}
-
 struct FcSeg { const uint32_t* src; uint32_t lo, n; };            // a shard's fingerprints: rows [lo, lo + n)
 
 static int fc_check(const void* out, const kb_fp_class* list, size_t cap_list, const uint32_t* rep, const uint32_t* size,
@@ -295,8 +286,7 @@ static int fc_check(const void* out, const kb_fp_class* list, size_t cap_list, c
   if (!out) return KB_INVALID_ARGUMENT;
   if (cap_list > KB_FPC_LIST_MAX) { seterr(std::string(who) + ": cap_list is above KB_FPC_LIST_MAX"); return KB_INVALID_ARGUMENT; }
   if (cap_list && !list) { seterr(std::string(who) + ": list is NULL with cap_list > 0"); return KB_INVALID_ARGUMENT; }
-  if ((rep || size) && cap_rows < n) { seterr(std::string(who) + ": an output array is shorter than the capacity"); return KB_INVALID_ARGUMENT; }
-  return KB_OK;
+  return census_caps(who, out, nullptr, 0, 0, any_of(rep, size), cap_rows, n);
 }
 
 // The census over d_fp / d_run ([n], device) in scratch `buf` laid out by `p`, on stream st.  With `segs` the
@@ -335,9 +325,9 @@ static int fc_exec(void* buf, const FcPlan& p, hipStream_t st, const uint32_t* d
   tm.stop(st);
   HIPCHK(hipGetLastError());
   uint32_t acc[FA_WORDS];
-  std::vector<kb_fp_class> got(cap_list);
+  std::vector<kb_fp_class> got;
   HIPCHK(hipMemcpyAsync(acc, a.acc, sizeof acc, hipMemcpyDeviceToHost, st));
-  if (cap_list) HIPCHK(hipMemcpyAsync(got.data(), b + p.list, sizeof(kb_fp_class) * cap_list, hipMemcpyDeviceToHost, st));
+  HIPCHK(fetch(got, b + p.list, cap_list, st));
   if (rep && p.n) HIPCHK(hipMemcpyAsync(rep, a.rep, 4ull * p.n, hipMemcpyDeviceToHost, st));
   if (size && p.n) HIPCHK(hipMemcpyAsync(size, a.size, 4ull * p.n, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -360,66 +350,47 @@ extern "C" int kb_sim_fp_classes(kb_sim* s, kb_fp_classes* out, kb_fp_class* lis
                                  uint32_t* rep, uint32_t* size, size_t cap_rows) {
   if (!s) return KB_INVALID_ARGUMENT;
   { const int rc = fc_check(out, list, cap_list, rep, size, cap_rows, s->C, "kb_sim_fp_classes"); if (rc) return rc; }
+  { const int rc = census_gate(s, "kb_sim_fp_classes", {" and a class spans ranks", nullptr, nullptr}); if (rc) return rc; }
   const bool grp = is_group(s);
-  if (kind_of(s).rank) {
-    seterr("kb_sim_fp_classes: a rank handle holds its own rows only and a class spans ranks (use kb_sim_create or kb_sim_create_local)");
-    return KB_INVALID_OPERATION;
-  }
   (void)hipSetDevice(s->device);
   // what kb_sim_fingerprints does first: the rows whose view changed since their fingerprint was last taken
-  const std::vector<kb_sim*> hs = grp ? s->shards : std::vector<kb_sim*>{s};
-  for (kb_sim* t : hs) {
-    if (t->sp) { if (t->sp->R) k_sp_fp_all<<<(t->sp->R + 255) / 256, 256, 0, t->sp->st>>>(t->sp->d); }
-    else if (t->R) k_fp_all<<<(t->R + 3) / 4, 256, 0, t->st>>>(t->d);
-    HIPCHK(hipGetLastError());
-    if (grp) HIPCHK(hipStreamSynchronize(t->sp ? t->sp->st : t->st));
-  }
+  { const int rc = route(s, R_ALL, 0, [&](auto* e) -> int {
+      const int rc = eng_refresh_fps(e);
+      if (!rc && grp) HIPCHK(hipStreamSynchronize(eng_stream(e)));
+      return rc;
+    });
+    if (rc) return rc; }
   uint32_t tfp = 0;
   { const int rc = kb_sim_true_fingerprint(s, &tfp); if (rc) return rc; }
-  kb_sim* h = hs[0];                                // its stream runs the census; every shard is on its device
-  hipStream_t st = h->sp ? h->sp->st : h->st;
   FcPlan p;
   if (!fc_plan(s->C, p)) { seterr("kb_sim_fp_classes: capacity above 2^30"); return KB_CAPACITY; }
-  { const int rc = fc_reserve(&s->fc_buf, &s->fc_cap, p.bytes); if (rc) return rc; }
+  { const int rc = dev_reserve(&s->fc_buf, &s->fc_cap, p.bytes, "fp_classes: scratch allocation failed"); if (rc) return rc; }
   std::vector<FcSeg> segs;
-  if (grp) for (kb_sim* t : hs) segs.push_back(FcSeg{(t->sp ? t->sp->d.fp : t->d.fp) + t->lo, t->lo, t->R});
-  return fc_exec(s->fc_buf, p, st, h->sp ? h->sp->d.fp : h->d.fp, h->sp ? h->sp->d.alive : h->d.alive, grp ? &segs : nullptr,
-                 tfp, h->sp ? h->sp->round : h->round, out, list, cap_list, n_list, rep, size, &s->fc_ms);
+  if (grp) route(s, R_ALL, 0, [&](auto* e) { segs.push_back(FcSeg{eng_fp(e) + e->lo, e->lo, e->R}); return KB_OK; });
+  // the first shard's stream runs the census; every shard is on its device
+  return route(s, R_FIRST, 0, [&](auto* e) {
+    return fc_exec(s->fc_buf, p, eng_stream(e), eng_fp(e), eng_alive(e), grp ? &segs : nullptr, tfp, e->round, out, list, cap_list,
+                   n_list, rep, size, &s->census_ms[CM_CLASSES]);
+  });
 }
 
-extern "C" int kb_sim_fp_classes_device_ms(kb_sim* s, double* ms) {
-  if (!s || !ms) return KB_INVALID_ARGUMENT;
-  *ms = s->fc_ms;
-  return KB_OK;
-}
+extern "C" int kb_sim_fp_classes_device_ms(kb_sim* s, double* ms) { return census_ms_get(s, CM_CLASSES, ms); }
 
 extern "C" int kb_fp_classes_of(int device, const uint32_t* fps, const uint8_t* running, size_t n, uint32_t true_fp,
                                 kb_fp_classes* out, kb_fp_class* list, size_t cap_list, size_t* n_list,
                                 uint32_t* rep, uint32_t* size, size_t cap_rows) {
   { const int rc = fc_check(out, list, cap_list, rep, size, cap_rows, n, "kb_fp_classes_of"); if (rc) return rc; }
   if (n && (!fps || !running)) return KB_INVALID_ARGUMENT;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { seterr("no HIP device"); return KB_NO_DEVICE; }
-  if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) { seterr("kb_fp_classes_of: no such device"); return KB_NO_DEVICE; }
+  OfScope o;
+  { const int rc = o.open(device, "kb_fp_classes_of"); if (rc) return rc; }
   FcPlan p;
   if (!fc_plan(n, p)) { seterr("kb_fp_classes_of: more than 2^30 rows"); return KB_CAPACITY; }
-  void* buf = nullptr; size_t cap = 0;
-  { const int rc = fc_reserve(&buf, &cap, p.bytes); if (rc) return rc; }
-  hipStream_t st = nullptr;
-  int rc = KB_IO_ERROR;
-  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess) {
-    char* b = static_cast<char*>(buf);
-    rc = [&]() -> int {
-      if (n) {
-        HIPCHK(hipMemcpyAsync(b + p.fp, fps, 4 * n, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(b + p.run, running, n, hipMemcpyHostToDevice, st));
-      }
-      return fc_exec(buf, p, st, reinterpret_cast<const uint32_t*>(b + p.fp), reinterpret_cast<const uint8_t*>(b + p.run), nullptr,
-                     true_fp, -1, out, list, cap_list, n_list, rep, size, nullptr);
-    }();
-    (void)hipStreamSynchronize(st);
-    (void)hipStreamDestroy(st);
-  } else seterr("kb_fp_classes_of: stream");
-  (void)hipFree(buf);
-  return rc;
+  { const int rc = dev_reserve(&o.buf, &o.cap, p.bytes, "fp_classes: scratch allocation failed"); if (rc) return rc; }
+  char* b = static_cast<char*>(o.buf);
+  if (n) {
+    HIPCHK(hipMemcpyAsync(b + p.fp, fps, 4 * n, hipMemcpyHostToDevice, o.st));
+    HIPCHK(hipMemcpyAsync(b + p.run, running, n, hipMemcpyHostToDevice, o.st));
+  }
+  return fc_exec(o.buf, p, o.st, reinterpret_cast<const uint32_t*>(b + p.fp), reinterpret_cast<const uint8_t*>(b + p.run), nullptr,
+                 true_fp, -1, out, list, cap_list, n_list, rep, size, nullptr);
 }

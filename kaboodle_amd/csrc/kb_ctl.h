@@ -10,6 +10,9 @@
 //   row_fp(e, node, fp)           one row's fingerprint
 //   lat_column(e, node, lat)      the latency column (dense with track_latency; else left empty)
 //   fold_stats(e)                 the per-workgroup partial counters folded into d.stats
+//   eng_stream(e)                 the engine's stream (the census frame, kb_censusframe.h, and the three below)
+//   eng_fp(e), eng_alive(e)       the device's fingerprints and running flags, per id
+//   eng_refresh_fps(e)            the launch that refolds the rows whose fingerprint is stale
 // Included by kb_sim.hip after both engines, before the API surface.
 #pragma once
 

@@ -225,19 +225,17 @@ static int lc_exec(void* buf, const LcPlan& pl, kb::LcArgs a, hipStream_t st, ui
   tm.stop(st);
   HIPCHK(hipGetLastError());
   unsigned long long head[kb::LC_HEAD];
-  std::vector<uint32_t> mb(C), mn(C), mx(C), rcnt(want_rows ? R : 0);
-  std::vector<uint64_t> sum(C), rsum(want_rows ? R : 0);
-  std::vector<uint8_t> alive(R);
+  std::vector<uint32_t> mb, mn, mx, rcnt;
+  std::vector<uint64_t> sum, rsum;
+  std::vector<uint8_t> alive;
   HIPCHK(hipMemcpyAsync(head, a.head, sizeof head, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(mb.data(), a.mb, 4ull * C, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(mn.data(), a.mn, 4ull * C, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(mx.data(), a.mx, 4ull * C, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(sum.data(), a.sum, 8ull * C, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(alive.data(), a.alive, R, hipMemcpyDeviceToHost, st));
-  if (want_rows) {
-    HIPCHK(hipMemcpyAsync(rcnt.data(), a.rcnt, 4ull * R, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(rsum.data(), a.rsum, 8ull * R, hipMemcpyDeviceToHost, st));
-  }
+  HIPCHK(fetch(mb, a.mb, C, st));
+  HIPCHK(fetch(mn, a.mn, C, st));
+  HIPCHK(fetch(mx, a.mx, C, st));
+  HIPCHK(fetch(sum, a.sum, C, st));
+  HIPCHK(fetch(alive, a.alive, R, st));
+  HIPCHK(fetch(rcnt, a.rcnt, want_rows ? R : 0, st));
+  HIPCHK(fetch(rsum, a.rsum, want_rows ? R : 0, st));
   HIPCHK(hipStreamSynchronize(st));
   p.ms += tm.ms();
   for (uint32_t k = 0; k < kb::LC_HEAD; ++k) p.head[k] += head[k];
@@ -267,12 +265,8 @@ static void lc_summary(const LcPart& p, int32_t round, kb_lat_census* out) {
 }
 static void lc_deliver(const LcPart& p, uint32_t* measured_by, uint64_t* sum_ms, uint32_t* min_ms, uint32_t* max_ms,
                        uint32_t* measured, uint64_t* row_sum_ms) {
-  if (measured_by) memcpy(measured_by, p.mb.data(), 4 * p.mb.size());
-  if (sum_ms) memcpy(sum_ms, p.sum.data(), 8 * p.sum.size());
-  if (min_ms) memcpy(min_ms, p.mn.data(), 4 * p.mn.size());
-  if (max_ms) memcpy(max_ms, p.mx.data(), 4 * p.mx.size());
-  if (measured) memcpy(measured, p.rcnt.data(), 4 * p.rcnt.size());
-  if (row_sum_ms) memcpy(row_sum_ms, p.rsum.data(), 8 * p.rsum.size());
+  deliver(measured_by, p.mb); deliver(sum_ms, p.sum); deliver(min_ms, p.mn); deliver(max_ms, p.mx);
+  deliver(measured, p.rcnt); deliver(row_sum_ms, p.rsum);
 }
 
 // one leaf's pass (route() hands every shard of a group here in turn)
@@ -285,34 +279,16 @@ static int lc_leaf(kb_sim* s, bool want_rows, LcPart& p) {
   kb::LcArgs a{};
   a.lat = d.lat; a.bits = d.bits + (size_t)s->lo * d.NWR; a.alive = d.alive + s->lo;   // d.bits is biased by -lo rows
   a.R = s->R; a.RS = RS; a.C = s->C; a.NWR = d.NWR;
-  const double before = p.ms;
-  const int rc = lc_exec(s->lc_buf, pl, a, s->st, s->lo, want_rows, p);
-  s->lc_ms = p.ms - before;
-  return rc;
+  return lc_exec(s->lc_buf, pl, a, s->st, s->lo, want_rows, p);
 }
-static int lc_leaf(SpSim*, bool, LcPart&) { seterr("kb_sim_latency_census: sparse rows keep no latency table"); return KB_INVALID_OPERATION; }
-
-static int lc_check(const void* out, const void* ids_any, size_t cap_ids, size_t n_ids, const void* rows_any, size_t cap_rows,
-                    size_t n_rows, const char* who) {
-  if (!out) return KB_INVALID_ARGUMENT;
-  if ((ids_any && cap_ids < n_ids) || (rows_any && cap_rows < n_rows)) {
-    seterr(std::string(who) + ": an output array is shorter than the capacity"); return KB_INVALID_ARGUMENT;
-  }
-  return KB_OK;
-}
-#define LC_ANY_IDS (measured_by ? (const void*)measured_by : sum_ms ? (const void*)sum_ms : min_ms ? (const void*)min_ms : (const void*)max_ms)
-#define LC_ANY_ROWS (measured ? (const void*)measured : (const void*)row_sum_ms)
+static int lc_leaf(SpSim*, bool, LcPart&) { return KB_INVALID_OPERATION; }   // not reached: census_gate refuses sparse rows
 
 extern "C" int kb_sim_latency_census(kb_sim* s, kb_lat_census* out, uint32_t* measured_by, uint64_t* sum_ms, uint32_t* min_ms,
                                      uint32_t* max_ms, size_t cap_ids, uint32_t* measured, uint64_t* row_sum_ms, size_t cap_rows) {
   if (!s) return KB_INVALID_ARGUMENT;
-  { const int rc = lc_check(out, LC_ANY_IDS, cap_ids, s->C, LC_ANY_ROWS, cap_rows, s->C, "kb_sim_latency_census"); if (rc) return rc; }
-  const Kind kd = kind_of(s);
-  if (kd.sparse) { seterr("kb_sim_latency_census: sparse rows keep no latency table"); return KB_INVALID_OPERATION; }
-  if (kd.rank) {
-    seterr("kb_sim_latency_census: a rank handle holds its own rows only (use kb_sim_create or kb_sim_create_local)");
-    return KB_INVALID_OPERATION;
-  }
+  { const int rc = census_caps("kb_sim_latency_census", out, any_of(measured_by, sum_ms, min_ms, max_ms), cap_ids, s->C,
+                               any_of(measured, row_sum_ms), cap_rows, s->C); if (rc) return rc; }
+  { const int rc = census_gate(s, "kb_sim_latency_census", {"", "keep no latency table", nullptr}); if (rc) return rc; }
   if (!s->cfg.track_latency) { seterr("kb_sim_latency_census: the handle was created without track_latency"); return KB_INVALID_OPERATION; }
   LcPart p;
   lc_part_init(p, s->C, s->C);
@@ -320,64 +296,51 @@ extern "C" int kb_sim_latency_census(kb_sim* s, kb_lat_census* out, uint32_t* me
   int32_t round = 0;
   { const int rc = route(s, R_ALL, 0, [&](auto* e) { return lc_leaf(e, want_rows, p); }); if (rc) return rc; }
   { const int rc = route(s, R_FIRST, 0, [&](auto* e) { round = e->round; return KB_OK; }); if (rc) return rc; }
-  s->lc_ms = p.ms;
+  s->census_ms[CM_LAT] = p.ms;
   lc_summary(p, round, out);
   lc_deliver(p, measured_by, sum_ms, min_ms, max_ms, measured, row_sum_ms);
   return KB_OK;
 }
 
-extern "C" int kb_sim_latency_census_device_ms(kb_sim* s, double* ms) {
-  if (!s || !ms) return KB_INVALID_ARGUMENT;
-  *ms = s->lc_ms;
-  return KB_OK;
-}
+extern "C" int kb_sim_latency_census_device_ms(kb_sim* s, double* ms) { return census_ms_get(s, CM_LAT, ms); }
 
 extern "C" int kb_latency_census_of(int device, const uint16_t* lat, const uint8_t* member, const uint8_t* running, size_t n_ids,
                                     size_t n_rows, kb_lat_census* out, uint32_t* measured_by, uint64_t* sum_ms, uint32_t* min_ms,
                                     uint32_t* max_ms, size_t cap_ids, uint32_t* measured, uint64_t* row_sum_ms, size_t cap_rows) {
-  { const int rc = lc_check(out, LC_ANY_IDS, cap_ids, n_ids, LC_ANY_ROWS, cap_rows, n_rows, "kb_latency_census_of"); if (rc) return rc; }
+  { const int rc = census_caps("kb_latency_census_of", out, any_of(measured_by, sum_ms, min_ms, max_ms), cap_ids, n_ids,
+                               any_of(measured, row_sum_ms), cap_rows, n_rows); if (rc) return rc; }
   if (n_ids && n_rows && (!lat || !member || !running)) return KB_INVALID_ARGUMENT;
   if (n_ids > (1u << 24) || n_rows > (1u << 26)) { seterr("kb_latency_census_of: more than 2^24 ids or 2^26 rows"); return KB_CAPACITY; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { seterr("no HIP device"); return KB_NO_DEVICE; }
-  if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) { seterr("kb_latency_census_of: no such device"); return KB_NO_DEVICE; }
+  std::vector<uint32_t> hb;                         // the member bits and running flags as uploaded: they outlive the stream
+  std::vector<uint8_t> ha;
+  OfScope o;
+  { const int rc = o.open(device, "kb_latency_census_of"); if (rc) return rc; }
   LcPart p;
   lc_part_init(p, n_ids, n_rows);
-  if (!n_ids || !n_rows) { lc_summary(p, -1, out); lc_deliver(p, measured_by, sum_ms, min_ms, max_ms, measured, row_sum_ms); return KB_OK; }
-  // the layout of a handle: columns of lat_stride(rows) cells, bit rows of W/32 words (W: whole 8192-id steps)
-  const uint32_t C = (uint32_t)n_ids, R = (uint32_t)n_rows, RS = lat_stride(R), NWR = (C + 8191) / 8192 * 8192 / 32;
-  std::vector<uint32_t> hb((size_t)R * NWR, 0u);
-  for (size_t i = 0; i < R; ++i)
-    for (size_t j = 0; j < C; ++j) if (member[i * C + j]) hb[i * NWR + (j >> 5)] |= 1u << (j & 31);
-  std::vector<uint8_t> ha(R);
-  for (size_t i = 0; i < R; ++i) ha[i] = running[i] != 0;
-  const LcPlan pl = lc_plan(C, RS);
-  const size_t lat_b = 2ull * C * RS, bits_b = 4ull * R * NWR, o_bits = (lat_b + 255) & ~(size_t)255,
-               o_alive = o_bits + bits_b, o_scr = (o_alive + R + 255) & ~(size_t)255;
-  char* buf = nullptr;
-  if (hipMalloc((void**)&buf, o_scr + pl.bytes) != hipSuccess) { seterr("kb_latency_census_of: device allocation failed"); return KB_CAPACITY; }
-  hipStream_t st = nullptr;
-  int rc = KB_IO_ERROR;
-  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess) {
-    rc = [&]() -> int {
-      HIPCHK(hipMemsetAsync(buf, 0xFF, lat_b, st));                                    // the padding rows: None
-      HIPCHK(hipMemcpy2DAsync(buf, 2ull * RS, lat, 2ull * R, 2ull * R, C, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(buf + o_bits, hb.data(), bits_b, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(buf + o_alive, ha.data(), R, hipMemcpyHostToDevice, st));
-      kb::LcArgs a{};
-      a.lat = reinterpret_cast<const uint16_t*>(buf); a.bits = reinterpret_cast<const uint32_t*>(buf + o_bits);
-      a.alive = reinterpret_cast<const uint8_t*>(buf + o_alive);
-      a.R = R; a.RS = RS; a.C = C; a.NWR = NWR;
-      return lc_exec(buf + o_scr, pl, a, st, 0, measured || row_sum_ms, p);
-    }();
-    (void)hipStreamSynchronize(st);
-    (void)hipStreamDestroy(st);
-  } else seterr("kb_latency_census_of: stream");
-  (void)hipFree(buf);
-  if (rc) return rc;
+  if (n_ids && n_rows) {
+    // the layout of a handle: columns of lat_stride(rows) cells, bit rows of W/32 words (W: whole 8192-id steps)
+    const uint32_t C = (uint32_t)n_ids, R = (uint32_t)n_rows, RS = lat_stride(R), NWR = (C + 8191) / 8192 * 8192 / 32;
+    hb.assign((size_t)R * NWR, 0u);
+    for (size_t i = 0; i < R; ++i)
+      for (size_t j = 0; j < C; ++j) if (member[i * C + j]) hb[i * NWR + (j >> 5)] |= 1u << (j & 31);
+    ha.resize(R);
+    for (size_t i = 0; i < R; ++i) ha[i] = running[i] != 0;
+    const LcPlan pl = lc_plan(C, RS);
+    const size_t lat_b = 2ull * C * RS, bits_b = 4ull * R * NWR, o_bits = (lat_b + 255) & ~(size_t)255,
+                 o_alive = o_bits + bits_b, o_scr = (o_alive + R + 255) & ~(size_t)255;
+    { const int rc = dev_reserve(&o.buf, &o.cap, o_scr + pl.bytes, "kb_latency_census_of: device allocation failed"); if (rc) return rc; }
+    char* buf = static_cast<char*>(o.buf);
+    HIPCHK(hipMemsetAsync(buf, 0xFF, lat_b, o.st));                                    // the padding rows: None
+    HIPCHK(hipMemcpy2DAsync(buf, 2ull * RS, lat, 2ull * R, 2ull * R, C, hipMemcpyHostToDevice, o.st));
+    HIPCHK(hipMemcpyAsync(buf + o_bits, hb.data(), bits_b, hipMemcpyHostToDevice, o.st));
+    HIPCHK(hipMemcpyAsync(buf + o_alive, ha.data(), R, hipMemcpyHostToDevice, o.st));
+    kb::LcArgs a{};
+    a.lat = reinterpret_cast<const uint16_t*>(buf); a.bits = reinterpret_cast<const uint32_t*>(buf + o_bits);
+    a.alive = reinterpret_cast<const uint8_t*>(buf + o_alive);
+    a.R = R; a.RS = RS; a.C = C; a.NWR = NWR;
+    { const int rc = lc_exec(buf + o_scr, pl, a, o.st, 0, measured || row_sum_ms, p); if (rc) return rc; }
+  }
   lc_summary(p, -1, out);
   lc_deliver(p, measured_by, sum_ms, min_ms, max_ms, measured, row_sum_ms);
   return KB_OK;
 }
-#undef LC_ANY_IDS
-#undef LC_ANY_ROWS

@@ -207,19 +207,15 @@ __global__ __launch_bounds__(RC_THREADS) void k_rc_pairs(RcArgs a) {
 extern "C" int kb_sim_reciprocity(kb_sim* s, kb_reciprocity* out, uint32_t* mutual, uint32_t* lacks, uint32_t* lacked_by,
                                   size_t cap_rows, uint32_t* pairs, size_t cap_pairs) {
   if (!s || !out) return KB_INVALID_ARGUMENT;
-  if (kind_of(s).sparse) {
-    seterr("kb_sim_reciprocity: sparse rows need an O(entries) algorithm of their own (not built yet)"); return KB_INVALID_OPERATION;
-  }
-  if (kind_of(s).rank) {
-    seterr("kb_sim_reciprocity: a rank handle holds its own rows only; the census needs every rank's (use kb_sim_create or kb_sim_create_local)");
-    return KB_INVALID_OPERATION;
-  }
-  if ((mutual || lacks || lacked_by) && cap_rows < s->C) {
-    seterr("kb_sim_reciprocity: an output array is shorter than the capacity"); return KB_INVALID_ARGUMENT;
-  }
+  { const int rc = census_gate(s, "kb_sim_reciprocity", {"; the census needs every rank's", "need an O(entries) algorithm of their own (not built yet)", nullptr});
+    if (rc) return rc; }
+  { const int rc = census_caps("kb_sim_reciprocity", out, nullptr, 0, 0, any_of(mutual, lacks, lacked_by), cap_rows, s->C); if (rc) return rc; }
   kb_sim* h = is_group(s) ? s->shards[0] : s;     // owns the scratch and the stream; every shard is on its device
   (void)hipSetDevice(h->device);
-  if (is_group(s)) for (kb_sim* t : s->shards) HIPCHK(hipStreamSynchronize(t->st));
+  if (is_group(s)) {
+    const int rc = route(s, R_ALL, 0, [](auto* e) -> int { HIPCHK(hipStreamSynchronize(eng_stream(e))); return KB_OK; });
+    if (rc) return rc;
+  }
   const Dev& d = h->d;
   const uint32_t C = s->C, nb = (C + RC_B - 1) / RC_B;
   // scratch: the three masks of k_cs_masks, then (zeroed each call) the pair counter, the counts, the flags
@@ -249,12 +245,12 @@ extern "C" int kb_sim_reciprocity(kb_sim* s, kb_reciprocity* out, uint32_t* mutu
   k_rc_count<<<dim3(nb, nb), RC_THREADS, 0, h->st>>>(a);
   tm.stop(h->st);
   HIPCHK(hipGetLastError());
-  std::vector<uint32_t> cnt(3ull * C);
-  std::vector<uint8_t> alive(C);
-  HIPCHK(hipMemcpyAsync(cnt.data(), a.cnt, 12ull * C, hipMemcpyDeviceToHost, h->st));
-  HIPCHK(hipMemcpyAsync(alive.data(), d.alive, C, hipMemcpyDeviceToHost, h->st));
+  std::vector<uint32_t> cnt;
+  std::vector<uint8_t> alive;
+  HIPCHK(fetch(cnt, a.cnt, 3ull * C, h->st));
+  HIPCHK(fetch(alive, d.alive, C, h->st));
   HIPCHK(hipStreamSynchronize(h->st));
-  s->rc_ms = tm.ms();
+  s->census_ms[CM_RECIP] = tm.ms();
   memset(out, 0, sizeof *out);
   out->round = h->round;
   out->max_mutual_row = KB_CENSUS_NONE;
@@ -267,30 +263,26 @@ extern "C" int kb_sim_reciprocity(kb_sim* s, kb_reciprocity* out, uint32_t* mutu
     if (mu > out->max_mutual) { out->max_mutual = mu; out->max_mutual_row = i; }
   }
   out->mutual_pairs = msum / 2;
-  if (mutual) memcpy(mutual, cnt.data(), 4ull * C);
-  if (lacks) memcpy(lacks, cnt.data() + C, 4ull * C);
-  if (lacked_by) memcpy(lacked_by, cnt.data() + 2ull * C, 4ull * C);
+  deliver(mutual, cnt.data(), C);
+  deliver(lacks, cnt.data() + C, C);
+  deliver(lacked_by, cnt.data() + 2ull * C, C);
   if (!pairs || !out->mutual_pairs || out->mutual_pairs > cap_pairs) return KB_OK;
   // the pair list: a device buffer and a host vector for exactly the known total (8 bytes each per pair), grown when
   // a later call needs more; the total is at most cap_pairs, so the caller's own 8 * cap_pairs buffer bounds both
   const uint64_t np = out->mutual_pairs;
-  if (h->rc_pairs_cap < np) {
-    if (h->rc_pairs) { (void)hipFree(h->rc_pairs); h->rc_pairs = nullptr; h->rc_pairs_cap = 0; }
-    if (hipMalloc((void**)&h->rc_pairs, 8ull * np) != hipSuccess) { h->rc_pairs = nullptr; seterr("reciprocity: pair buffer allocation failed"); return KB_CAPACITY; }
-    h->rc_pairs_cap = np;
-  }
-  a.pairs = reinterpret_cast<uint2*>(h->rc_pairs); a.cap = np;
+  { const int rc = dev_reserve(&h->rc_pairs, &h->rc_pairs_cap, 8ull * np, "reciprocity: pair buffer allocation failed"); if (rc) return rc; }
+  a.pairs = static_cast<uint2*>(h->rc_pairs); a.cap = np;
   CsTimer tp;
   if (!tp.start(h->st)) { seterr("reciprocity: events"); return KB_IO_ERROR; }
   k_rc_pairs<<<dim3(nb, nb), RC_THREADS, 0, h->st>>>(a);
   tp.stop(h->st);
   HIPCHK(hipGetLastError());
-  std::vector<uint64_t> pl(np);
+  std::vector<uint64_t> pl;
   unsigned long long got = 0;
   HIPCHK(hipMemcpyAsync(&got, a.npairs, 8, hipMemcpyDeviceToHost, h->st));
-  HIPCHK(hipMemcpyAsync(pl.data(), a.pairs, 8ull * np, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(fetch(pl, a.pairs, np, h->st));
   HIPCHK(hipStreamSynchronize(h->st));
-  s->rc_ms += tp.ms();
+  s->census_ms[CM_RECIP] += tp.ms();
   if (got != np) { seterr("reciprocity: the pair pass and the counts disagree"); return KB_IO_ERROR; }
   for (uint64_t& v : pl) v = (v << 32) | (v >> 32);              // uint2 (i, j) in memory = j << 32 | i: sort by (i, j)
   std::sort(pl.begin(), pl.end());
@@ -299,8 +291,4 @@ extern "C" int kb_sim_reciprocity(kb_sim* s, kb_reciprocity* out, uint32_t* mutu
   return KB_OK;
 }
 
-extern "C" int kb_sim_reciprocity_device_ms(kb_sim* s, double* ms) {
-  if (!s || !ms) return KB_INVALID_ARGUMENT;
-  *ms = s->rc_ms;
-  return KB_OK;
-}
+extern "C" int kb_sim_reciprocity_device_ms(kb_sim* s, double* ms) { return census_ms_get(s, CM_RECIP, ms); }

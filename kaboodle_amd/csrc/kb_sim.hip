@@ -335,6 +335,8 @@ __global__ __launch_bounds__(256) void k_lat_column(Dev d, uint32_t node, uint16
 }
 
 namespace kb { struct SpSim; }
+enum CensusMs { CM_VIEW, CM_RECIP, CM_CLASSES, CM_LAT, CM_AGE, CM_N };   // kb_sim::census_ms (kb_censusframe.h)
+
 struct kb_sim {
   kb_config cfg;
   SpSim* sp = nullptr;                 // KB_VARIANT_SPARSE_ROWS: the sparse-row engine answers every call
@@ -420,12 +422,10 @@ struct kb_sim {
   uint64_t host_syncs = 0;             // host waits on the device (stream syncs, pinned hand-offs) since creation
   uint32_t ncu = 256;
   uint32_t* cs_buf = nullptr;          // the census's scratch (kb_census.h), allocated by the first census
-  double cs_ms = 0;                    // device time of the last census
   uint32_t* rc_buf = nullptr;          // the reciprocity census's scratch (kb_recip.h), allocated by its first call
-  uint32_t* rc_pairs = nullptr; uint64_t rc_pairs_cap = 0;   // its pair list (entries), grown on demand
-  double rc_ms = 0;                    // device time of the last reciprocity census
+  void* rc_pairs = nullptr; size_t rc_pairs_cap = 0;   // its pair list, bytes; grown on demand
   void* fc_buf = nullptr; size_t fc_cap = 0;   // the class census's scratch (kb_classes.h), bytes; grown on demand
-  double fc_ms = 0;                    // device time of the last class census
+  double census_ms[CM_N] = {};         // device time of the last census of each kind, on the handle that was asked
   bool debug_waves = false;
   size_t lds_per_cu = 65536;
   // kb_sim_create_local: a façade over `world` in-process shards (one host thread each per step)
@@ -445,8 +445,6 @@ struct kb_sim {
   hipGraph_t wave_graph = nullptr; hipGraphExec_t wave_exec = nullptr;
   uint64_t buf_gen = 0, wave_gen = ~0ull;
   uint32_t* lc_buf = nullptr;          // the latency census's scratch (kb_latcensus.h), allocated by its first call
-  double lc_ms = 0;                    // device time of the last latency census
-  double ag_ms = 0;                    // device time of the last contact-age census
   double sn_ms = 0;                    // device time of the last snapshot pack, or of the restore that made the handle
 };
 
@@ -1844,6 +1842,16 @@ extern "C" int kb_sim_fingerprint(kb_sim* s, uint32_t node, uint32_t* fp) {
   if (chk(s, node) || !fp) return KB_INVALID_ARGUMENT;
   return route(s, R_OWNER, node, [&](auto* e) { return row_fp(e, node, fp); });
 }
+// the census frame's hooks (kb_ctl.h): the engine's stream, its device fingerprints and running flags, and the
+// refresh of the rows whose view changed since their fingerprint was last taken
+static hipStream_t eng_stream(kb_sim* s) { return s->st; }
+static const uint32_t* eng_fp(kb_sim* s) { return s->d.fp; }
+static const uint8_t* eng_alive(kb_sim* s) { return s->d.alive; }
+static int eng_refresh_fps(kb_sim* s) {
+  if (s->R) k_fp_all<<<(s->R + 3) / 4, 256, 0, s->st>>>(s->d);
+  HIPCHK(hipGetLastError());
+  return KB_OK;
+}
 // all ids; 0 for non-running ids and for rows held by other shards
 static int eng_fingerprints(kb_sim* s, uint32_t* fps) {
   k_fp_all<<<(s->R + 3) / 4, 256, 0, s->st>>>(s->d);
@@ -2273,6 +2281,9 @@ extern "C" int kb_sim_debug_fold(kb_sim* s, const kb_fold_probe* p) {
   }
   return KB_OK;
 }
+
+// ---- the censuses' shared host frame ------------------------------------------------------------------------
+#include "kb_censusframe.h"
 
 // ---- the view census (include/kaboodle_census.h) ----------------------------------------------------------
 #include "kb_census.h"

@@ -78,9 +78,7 @@ struct SpSim {
   double round_ms = 0; uint64_t round_n = 0;
   uint64_t host_syncs = 0;
   uint32_t* cs_buf = nullptr;                       // the census's scratch (kb_census.h), allocated by the first census
-  double cs_ms = 0;                                 // device time of the last census
   uint32_t* ag_buf = nullptr;                       // the contact-age census's scratch (kb_agecensus.h), allocated by its first call
-  double ag_ms = 0;                                 // device time of the last contact-age census
   // external peers
   std::vector<uint8_t> h_ext;
   size_t n_ext = 0;
@@ -796,6 +794,15 @@ static int row_fp(SpSim* S, uint32_t node, uint32_t* fp) {
   k_sp_fp_one<<<1, 64, 0, S->st>>>(S->d, node);
   HIPCHK(hipMemcpyAsync(fp, S->d.fp + node, 4, hipMemcpyDeviceToHost, S->st));
   HIPCHK(hipStreamSynchronize(S->st));
+  return KB_OK;
+}
+// the census frame's hooks (kb_ctl.h)
+static hipStream_t eng_stream(SpSim* S) { return S->st; }
+static const uint32_t* eng_fp(SpSim* S) { return S->d.fp; }
+static const uint8_t* eng_alive(SpSim* S) { return S->d.alive; }
+static int eng_refresh_fps(SpSim* S) {
+  if (S->R) k_sp_fp_all<<<(S->R + 255) / 256, 256, 0, S->st>>>(S->d);
+  HIPCHK(hipGetLastError());
   return KB_OK;
 }
 // all ids; 0 for non-running ids and for rows held by other shards

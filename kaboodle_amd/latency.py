@@ -13,7 +13,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-KB_CENSUS_NONE = 0xFFFFFFFF
+from ._ffi import KB_CENSUS_NONE, diff_results
+
 KB_LATENCY_NONE = 0xFFFFFFFF
 KB_LAT_HIST = 17
 LAT_NONE = 0xFFFF                 # None in a u16 latency table
@@ -42,16 +43,7 @@ class LatencyCensus:
 
     def same_as(self, other: "LatencyCensus") -> list[str]:
         """The differences to another latency census (empty: identical summary and arrays)."""
-        out = [f"summary.{k}: {v} != {other.summary[k]}" for k, v in self.summary.items() if other.summary[k] != v]
-        for name in ARRAYS:
-            a, b = getattr(self, name), getattr(other, name)
-            if (a is None) != (b is None):
-                out.append(f"{name}: only one side has the array")
-            elif a is not None and not np.array_equal(a, b):
-                bad = np.flatnonzero(a != b) if a.shape == b.shape else [0]
-                out.append(f"{name}: {len(bad)} differ, first id {bad[0]}" +
-                           (f": {a[bad[0]]} != {b[bad[0]]}" if a.shape == b.shape else " (shapes)"))
-        return out
+        return diff_results(self, other, ARRAYS)
 
 
 def _finish(n_ids, n_rows, observers, round_, peers, rows, vals, orphans, arrays) -> LatencyCensus:

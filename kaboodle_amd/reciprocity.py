@@ -11,7 +11,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-KB_CENSUS_NONE = 0xFFFFFFFF
+from ._ffi import KB_CENSUS_NONE, diff_results
+
 SUMMARY_FIELDS = ("round", "observers", "mutual_pairs", "oneway_pairs", "rows_mutual", "rows_oneway",
                   "max_mutual_row", "max_mutual", "pairs_listed")
 
@@ -31,15 +32,7 @@ class Reciprocity:
 
     def same_as(self, other: "Reciprocity") -> list[str]:
         """The differences to another reciprocity census (empty: identical summary, arrays and pair list)."""
-        out = [f"summary.{k}: {v} != {other.summary[k]}" for k, v in self.summary.items() if other.summary[k] != v]
-        for name in ("mutual", "lacks", "lacked_by"):
-            a, b = getattr(self, name), getattr(other, name)
-            if not np.array_equal(a, b):
-                bad = np.flatnonzero(a != b)
-                out.append(f"{name}: {len(bad)} differ, first id {bad[0]}: {a[bad[0]]} != {b[bad[0]]}")
-        if not np.array_equal(self.pairs, other.pairs):
-            out.append(f"pairs: {len(self.pairs)} listed != {len(other.pairs)} listed, or other entries")
-        return out
+        return diff_results(self, other, ("mutual", "lacks", "lacked_by", "pairs"))
 
 
 def summarize(round_: int, observers: np.ndarray, mutual: np.ndarray, lacks: np.ndarray, pairs_listed: int) -> dict:

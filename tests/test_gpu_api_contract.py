@@ -17,8 +17,8 @@ from dataclasses import replace
 import pytest
 
 import parity
-from kaboodle_amd._ffi import (KB_INIT_CONVERGED, KB_VARIANT_SPARSE_ROWS, KbBroadcast, KbPeerState, KbProbeResponse,
-                               KbStats, KbUnicast, Sim, SimConfig, wire_addr)
+from kaboodle_amd._ffi import (KB_INIT_CONVERGED, KB_VARIANT_SPARSE_ROWS, KbBroadcast, KbError, KbPeerState,
+                               KbProbeResponse, KbStats, KbUnicast, Sim, SimConfig, rccl_unique_id, wire_addr)
 
 CAP, N0, GAP = 64, 40, 3
 PAQ, TICK_MAX, MAXID = 8, 33, 32            # kb_device.h
@@ -323,3 +323,70 @@ def test_api_contract(kind):
     for line in bad:
         print(line)
     assert not bad, f"{len(bad)} of {len(log)} calls differ from the oracle, first: {bad[0]}"
+
+
+# ---- the five censuses against the handle kinds -------------------------------------------------------------------
+# What each census entry point does on each kind of handle: None = it answers, else (code, kb_last_error()), exact.
+# Capacity 96, 64 initial members, 2 rounds.  Dense handles track latency ("dense_nolat" is the one that does not).
+# "rank" is one rank of a one-rank kb_sim_create_rank world; "sparse_rank" the same over sparse rows (which refusal
+# comes first is part of the contract).
+CENSUSES = ("census", "reciprocity", "fp_classes", "latency_census", "age_census")
+_OWN_ROWS = " (use kb_sim_create or kb_sim_create_local)"
+_RC_SPARSE = (1, "kb_sim_reciprocity: sparse rows need an O(entries) algorithm of their own (not built yet)")
+_RC_RANK = (1, "kb_sim_reciprocity: a rank handle holds its own rows only; the census needs every rank's" + _OWN_ROWS)
+_FC_RANK = (1, "kb_sim_fp_classes: a rank handle holds its own rows only and a class spans ranks" + _OWN_ROWS)
+_LC_SPARSE = (1, "kb_sim_latency_census: sparse rows keep no latency table")
+_LC_RANK = (1, "kb_sim_latency_census: a rank handle holds its own rows only" + _OWN_ROWS)
+_LC_NOLAT = (1, "kb_sim_latency_census: the handle was created without track_latency")
+_AG_DENSE = (1, "kb_sim_age_census: dense rows are not answered yet (KB_VARIANT_SPARSE_ROWS handles are)")
+_AG_RANK = (1, "kb_sim_age_census: a rank handle holds its own rows only" + _OWN_ROWS)
+# kind -> (variant, shards, rank handle, track_latency), then the row of expectations in the order of CENSUSES
+CENSUS_MATRIX = {
+    "dense": ((0, 0, False, 1), (None, None, None, None, _AG_DENSE)),
+    "dense_nolat": ((0, 0, False, 0), (None, None, None, _LC_NOLAT, _AG_DENSE)),
+    "sparse": ((KB_VARIANT_SPARSE_ROWS, 0, False, 0), (None, _RC_SPARSE, None, _LC_SPARSE, None)),
+    "dense_x2": ((0, 2, False, 1), (None, None, None, None, _AG_DENSE)),
+    "sparse_x2": ((KB_VARIANT_SPARSE_ROWS, 2, False, 0), (None, _RC_SPARSE, None, _LC_SPARSE, None)),
+    "rank": ((0, 0, True, 1), (None, _RC_RANK, _FC_RANK, _LC_RANK, _AG_RANK)),     # the view census: its own rows
+    "sparse_rank": ((KB_VARIANT_SPARSE_ROWS, 0, True, 0), (None, _RC_SPARSE, _FC_RANK, _LC_SPARSE, _AG_RANK)),
+}
+CENSUS_CFG = SimConfig(capacity=96, initial_nodes=64, init_mode=KB_INIT_CONVERGED, loss=0.02, seed=5)
+
+
+@pytest.mark.gpu
+def test_census_refusal_matrix():
+    """Every census on every kind of handle answers or refuses with exactly the pinned code and text, and the
+    *_device_ms getters read 0.0 until their census has answered on that handle, > 0 afterwards, and on a group the
+    last call's time alone (a second call on the unchanged mesh is not the sum of both)."""
+    lib = parity.gpu_lib()
+    bad = []
+    for kind, ((variant, shards, rank, track), row) in CENSUS_MATRIX.items():
+        cfg = replace(CENSUS_CFG, variant=variant, track_latency=track)
+        kw = dict(rank=0, world=1, uid=rccl_unique_id(lib)) if rank else dict(shards=shards)
+        with Sim(lib, cfg, **kw) as g:
+            ms = {name: getattr(g, name + "_device_ms") for name in CENSUSES}
+            for name in CENSUSES:
+                assert ms[name]() == 0.0, f"{kind}: {name}_device_ms() on a fresh handle"
+            g.step(2)
+            for name, want in zip(CENSUSES, row):
+                try:
+                    getattr(g, name)()
+                    got = None
+                except KbError as e:
+                    got = (e.code, lib.fn["last_error"]().decode())
+                if got != want:
+                    bad.append(f"{kind}.{name}: got {got!r}, want {want!r}")
+                    continue
+                if want is not None:
+                    assert ms[name]() == 0.0, f"{kind}: {name}_device_ms() after a refusal"
+                    continue
+                first = ms[name]()
+                assert first > 0.0, f"{kind}: {name}_device_ms() after an answer"
+                if shards:
+                    getattr(g, name)()
+                    second = ms[name]()
+                    print(f"{kind}.{name}: device ms {first:.4f} then {second:.4f}")
+                    assert 0.0 < second < 2.0 * first, f"{kind}: {name}_device_ms() {first} then {second}: it accumulates"
+    for line in bad:
+        print(line)
+    assert not bad, f"{len(bad)} cells differ, first: {bad[0]}"
