@@ -16,6 +16,7 @@
 #include "kaboodle_classes.h"
 #include "kaboodle_latency.h"
 #include "kaboodle_age.h"
+#include "kaboodle_delta.h"
 
 namespace kb {
 
@@ -136,6 +137,23 @@ class Mesh {
                             arrays ? r.last_heard.data() : nullptr, r.last_heard.size(), p(r.suspects), p(r.ancient),
                             p(r.windowed), p(r.fresh), r.suspects.size()),
           "kb_sim_age_census");
+    return r;
+  }
+
+  // the view-delta census (kaboodle_delta.h; HIP library only, dense handles): what every view gained and lost since
+  // delta_mark().  Per id: the continuing rows whose view gained / lost it; per row: the ids its view gained, lost, and
+  // lost although they run.  advance = true makes the current state the baseline in the same pass; arrays = false asks
+  // for the summary alone.
+  struct DeltaCensus { kb_delta summary; std::vector<uint32_t> gained_by, lost_by, gained, lost, lost_live; };
+  void delta_mark() { check(kb_sim_delta_mark(h_), "kb_sim_delta_mark"); }
+  void delta_release() { check(kb_sim_delta_release(h_), "kb_sim_delta_release"); }
+  DeltaCensus delta_census(bool advance = true, bool arrays = true) {
+    DeltaCensus r;
+    if (arrays) for (auto* v : {&r.gained_by, &r.lost_by, &r.gained, &r.lost, &r.lost_live}) v->resize(capacity_);
+    auto p = [&](std::vector<uint32_t>& v) { return arrays ? v.data() : nullptr; };
+    check(kb_sim_delta_census(h_, &r.summary, p(r.gained_by), p(r.lost_by), r.gained_by.size(), p(r.gained), p(r.lost),
+                              p(r.lost_live), r.gained.size(), advance ? KB_DELTA_ADVANCE : 0u),
+          "kb_sim_delta_census");
     return r;
   }
 

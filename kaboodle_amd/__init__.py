@@ -143,6 +143,24 @@ class Mesh(Sim):
         unsharded or in-process shards; dense rows and rank shards raise KbError."""
         return super().age_census(arrays)
 
+    def delta_mark(self) -> None:
+        """Take (or replace) the baseline of the view-delta census (include/kaboodle_delta.h): a
+        device-side copy of the member bits and the running set as they are now.  Dense rows, unsharded or
+        in-process shards; sparse rows and rank shards raise KbError."""
+        super().delta_mark()
+
+    def delta_census(self, advance: bool = True, arrays: bool = True):
+        """What every view gained and lost since the mark, in one pass on the GPU: per id how many continuing rows
+        (running at the mark and now) gained and lost it, per row how many ids its view gained, lost, and lost
+        although they still run, and the sums by kind of id (learned, ghost_adds, detections, false_drops).  Returns a
+        `delta.DeltaCensus`.  advance=True makes the current state the baseline in the same pass, so one call per
+        round gives per-round deltas (delta.PairTracker); advance=False reads only."""
+        return super().delta_census(advance, arrays)
+
+    def delta_release(self) -> None:
+        """Free the baseline; delta_census raises KbError until the next delta_mark."""
+        super().delta_release()
+
 
 def latency_census_of(lat, member, running, arrays: bool = True, device: int = 0):
     """The latency census's GPU kernel over host arrays (kb_latency_census_of, a test surface): `lat` peer-major
@@ -155,6 +173,14 @@ def fp_classes_of(fps, running, true_fp: int, top: int = 16, arrays: bool = True
     """The class census's GPU kernels over host arrays (kb_fp_classes_of, a test surface): `classes.FpClasses`."""
     from ._ffi import fp_classes_of as _of
     return _of(lib(), fps, running, true_fp, top, arrays, device)
+
+
+def delta_of(bits_base, run_base, bits_now, run_now, external, row_lo: int = 0, rpw: int = 0, arrays: bool = True,
+             device: int = 0):
+    """The delta census's GPU kernel over host arrays (kb_delta_of, a test surface): member bits [rows][W/32] at the
+    mark and now, the two running sets and the external ids per id; a `delta.DeltaCensus`."""
+    from ._ffi import delta_of as _of
+    return _of(lib(), bits_base, run_base, bits_now, run_now, external, row_lo, rpw, arrays, device)
 
 
 def discover_mesh_member(mesh: "Mesh", prober=("192.0.2.1", 40000), max_rounds: int = 64):

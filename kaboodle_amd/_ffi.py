@@ -197,6 +197,25 @@ _AGEC_OUT = [C.POINTER(KbAgeCensus), *[C.POINTER(C.c_uint32)] * 4, C.POINTER(C.c
              *[C.POINTER(C.c_uint32)] * 4, C.c_size_t]
 
 
+KB_DELTA_ADVANCE = 1             # kb_sim_delta_census flags
+
+
+class KbDelta(C.Structure):
+    """kb_delta (include/kaboodle_delta.h)."""
+    _fields_ = [("round_base", C.c_int32), ("round", C.c_int32), ("continuing", C.c_uint32), ("new_rows", C.c_uint32),
+                ("ended_rows", C.c_uint32), ("changed_rows", C.c_uint32), ("changed_ids", C.c_uint32),
+                ("top_false_drop", C.c_uint32), ("top_false_drop_by", C.c_uint32), ("pad", C.c_uint32),
+                ("learned", C.c_uint64), ("ghost_adds", C.c_uint64), ("detections", C.c_uint64),
+                ("false_drops", C.c_uint64), ("ext_gained", C.c_uint64), ("ext_lost", C.c_uint64),
+                ("reserved", C.c_uint64 * 4)]
+
+    def as_dict(self) -> dict:
+        return _summary(self)
+
+
+_DELTA_OUT = [C.POINTER(KbDelta), *[C.POINTER(C.c_uint32)] * 2, C.c_size_t, *[C.POINTER(C.c_uint32)] * 3, C.c_size_t]
+
+
 KB_SNAPSHOT_VERSION = 1
 
 
@@ -395,6 +414,14 @@ _OPTIONAL = {
     # the contact-age census (include/kaboodle_age.h; HIP library only, the oracle answers through age.age_census_ref)
     "sim_age_census": (C.c_int, [C.c_void_p, *_AGEC_OUT]),
     "sim_age_census_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    # the view-delta census (include/kaboodle_delta.h; HIP library only, the oracle answers through delta.delta_ref)
+    "sim_delta_mark": (C.c_int, [C.c_void_p]),
+    "sim_delta_census": (C.c_int, [C.c_void_p, *_DELTA_OUT, C.c_uint32]),
+    "sim_delta_release": (C.c_int, [C.c_void_p]),
+    "sim_delta_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "delta_of": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32),
+                           C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32,
+                           *_DELTA_OUT]),
     # snapshot and restore (include/kaboodle_snapshot.h; HIP library only)
     "snapshot_info_of": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(KbSnapshotInfo)]),
     "sim_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
@@ -506,6 +533,28 @@ def _age_census_call(lib: SimLib, name: str, head: tuple, arrays: bool, n_ids: i
     return AgeCensus(out.as_dict(), *outs)
 
 
+def delta_of(lib: SimLib, bits_base, run_base, bits_now, run_now, external, row_lo: int = 0, rpw: int = 0,
+             arrays: bool = True, device: int = 0):
+    """kb_delta_of: the delta census's kernel over host arrays (a test surface, include/kaboodle_delta.h).  bits_base /
+    bits_now: uint32 [rows, W/32] member bits of the ids row_lo onwards (W = capacity rounded up to 8192); run_base /
+    run_now / external: a flag per id ([capacity]); rpw: rows per wave (0: the default).  A `DeltaCensus` with rounds
+    -1.  KbError(KB_NO_DEVICE) without a GPU."""
+    import numpy as np
+    from .delta import DeltaCensus
+    rb, rn, ex = (np.ascontiguousarray(np.asarray(a) != 0, dtype=np.uint8) for a in (run_base, run_now, external))
+    cap = len(rn)
+    b0, b1 = (np.ascontiguousarray(a, dtype=np.uint32) for a in (bits_base, bits_now))
+    nwr = (cap + 8191) // 8192 * 8192 // 32
+    if len(rb) != cap or len(ex) != cap or b0.shape != b1.shape or b0.ndim != 2 or b0.shape[1] != nwr:
+        raise ValueError("delta_of: array shapes do not match the capacity")
+    p8, p32 = (lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32)))
+    out = KbDelta()
+    outs, args = _out_arrays(arrays, (["u4"] * 2, cap), (["u4"] * 3, cap))
+    lib.call("delta_of", device, p32(b0), p8(rb), p32(b1), p8(rn), p8(ex), cap, row_lo, b0.shape[0], rpw,
+             C.byref(out), *args)
+    return DeltaCensus(out.as_dict(), *outs)
+
+
 class Sim:
     """A simulated mesh (one handle) bound to a SimLib.
 
@@ -530,6 +579,7 @@ class Sim:
         self.h = h
         self.capacity = cfg.capacity
         self.external: set[int] = set()      # ids marked by set_external (census_ref needs them on the oracle)
+        self._delta_base = None              # the host baseline of a library without kb_sim_delta_mark (the oracle)
 
     def shard_info(self):
         """(rank, world, lo, hi): the rows this handle holds."""
@@ -794,6 +844,55 @@ class Sim:
         """Device time of the last age_census() in ms (kb_sim_age_census_device_ms; HIP library only)."""
         return self._device_ms("age_census")
 
+    def delta_mark(self) -> None:
+        """Take or replace the baseline of the view-delta census (kb_sim_delta_mark, include/kaboodle_delta.h): a
+        device-side copy of the member bits and the running set as they are now.  A library without it (the CPU
+        oracle) keeps the same baseline on the host, from row() and scalars()."""
+        if "sim_delta_mark" not in self.lib.fn:
+            from .delta import host_state
+            self._delta_base = host_state(self)
+            return
+        self.lib.call("sim_delta_mark", self.h)
+
+    def delta_census(self, advance: bool = True, arrays: bool = True):
+        """The view-delta census (include/kaboodle_delta.h): a `DeltaCensus` with `summary` (dict of kb_delta) and,
+        over all ids, `gained_by`, `lost_by` per id and `gained`, `lost`, `lost_live` per row (None with
+        arrays=False: the summary alone), against the baseline of delta_mark().  advance=True (KB_DELTA_ADVANCE): the
+        baseline becomes the current state in the same pass; advance=False: strictly read-only.  KbError
+        (KB_INVALID_OPERATION, "no baseline") before a mark.  Computed on the device by kb_sim_delta_census (dense
+        handles, unsharded or in-process shards); a library without it (the CPU oracle) answers the same call through
+        delta.delta_ref from its host baseline, so both are compared through identical calls."""
+        if "sim_delta_census" not in self.lib.fn:
+            import numpy as np
+            from .delta import DeltaCensus, delta_ref, host_state
+            if self._delta_base is None:
+                raise KbError(KB_INVALID_OPERATION, "delta_census (no baseline)")
+            now = host_state(self)
+            ext = np.zeros(self.capacity, dtype=bool)
+            ext[list(self.external)] = True
+            (b0, r0, t0), (b1, r1, t1) = self._delta_base, now
+            d = delta_ref(b0, r0, b1, r1, ext, self.shard_info()[2], t0, t1)
+            if advance:
+                self._delta_base = now
+            return d if arrays else DeltaCensus(d.summary, None, None, None, None, None)
+        from .delta import DeltaCensus
+        out = KbDelta()
+        outs, args = _out_arrays(arrays, (["u4"] * 2, self.capacity), (["u4"] * 3, self.capacity))
+        self.lib.call("sim_delta_census", self.h, C.byref(out), *args, KB_DELTA_ADVANCE if advance else 0)
+        return DeltaCensus(out.as_dict(), *outs)
+
+    def delta_release(self) -> None:
+        """Free the baseline (kb_sim_delta_release); nothing happens when there is none."""
+        if "sim_delta_release" not in self.lib.fn:
+            self._delta_base = None
+            return
+        self.lib.call("sim_delta_release", self.h)
+
+    def delta_census_device_ms(self) -> float:
+        """Device time of the last delta_census() in ms (kb_sim_delta_device_ms; HIP library only); 0.0 before the
+        first answer."""
+        return self._device_ms("delta")
+
     def snapshot(self) -> bytes:
         """The mesh's state after the last completed round as one byte string (kb_sim_snapshot,
         include/kaboodle_snapshot.h): canonical, the same bytes from an unsharded handle and a group of shards.
@@ -820,6 +919,7 @@ class Sim:
         self.h = h
         self.capacity = self.cfg.capacity
         self.external = set()
+        self._delta_base = None
         return self
 
     def snapshot_device_ms(self) -> float:

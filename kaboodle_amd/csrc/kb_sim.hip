@@ -335,7 +335,7 @@ __global__ __launch_bounds__(256) void k_lat_column(Dev d, uint32_t node, uint16
 }
 
 namespace kb { struct SpSim; }
-enum CensusMs { CM_VIEW, CM_RECIP, CM_CLASSES, CM_LAT, CM_AGE, CM_N };   // kb_sim::census_ms (kb_censusframe.h)
+enum CensusMs { CM_VIEW, CM_RECIP, CM_CLASSES, CM_LAT, CM_AGE, CM_DELTA, CM_N };   // kb_sim::census_ms (kb_censusframe.h)
 
 struct kb_sim {
   kb_config cfg;
@@ -446,6 +446,11 @@ struct kb_sim {
   uint64_t buf_gen = 0, wave_gen = ~0ull;
   uint32_t* lc_buf = nullptr;          // the latency census's scratch (kb_latcensus.h), allocated by its first call
   double sn_ms = 0;                    // device time of the last snapshot pack, or of the restore that made the handle
+  // the view-delta census (kb_delta.h): this handle's baseline, taken by kb_sim_delta_mark, and the pass's scratch
+  uint32_t* dl_base = nullptr;         // [R][W/32] the rows' member bits at the mark (null: no baseline)
+  uint8_t* dl_run = nullptr;           // [C] the running set at the mark
+  int32_t dl_round = 0;                // the round of the mark
+  uint32_t* dl_buf = nullptr;          // the scratch, allocated by the first delta census
 };
 
 // allocation of this handle's device memory; row tables hold the local rows only and their pointer
@@ -2299,6 +2304,9 @@ extern "C" int kb_sim_debug_fold(kb_sim* s, const kb_fold_probe* p) {
 
 // ---- the contact-age census (include/kaboodle_age.h) -------------------------------------------------------
 #include "kb_agecensus.h"
+
+// ---- the view-delta census (include/kaboodle_delta.h) -------------------------------------------------------
+#include "kb_delta.h"
 
 // ---- snapshot and restore (include/kaboodle_snapshot.h) ----------------------------------------------------
 #include "kb_snapshot.h"
