@@ -316,7 +316,12 @@ int  kb_sim_dump_suspects(kb_sim* sim, uint32_t node, int32_t* out, size_t cap, 
    1 broadcast phase on the HBM bitset (a round with a Failed list), 2/4 Join responses from HBM scratch (sampled / complete),
    8 KnownPeers BIG group on the HBM bitset, 16 k_proc unsorted selection path, 32 Failed-list prep
    from HBM, 64 Join responses by wave, 128 KnownPeers BIG group in LDS, 256 Join responses by wave
-   from the rows in place).  Test surface.                                                          */
+   from the rows in place, 512 split wave 0: the deferred k_proc pass handled a BIG destination's inbox;
+   the mass-join paths: 1024 row pass with the rows staged in LDS and the broadcast lists read from HBM
+   (more than 1024 Joins or 2048 Faileds beside a Failed list), 2048 a KnownPeersRequest reply proven
+   oversize from a wrapped freshness log (more than 2048 entries in the window), 4096 Join responses of a
+   receiver with more than 1024 new joiners (their ids read from HBM), 8192 row shards: a Join response to
+   a joiner past the 1024 union slots crossed shards as a list).  Test surface.                      */
 int  kb_sim_debug_paths(kb_sim* sim, uint32_t* mask);
 /* Development counters since creation (cap >= 3; slots 3-4 with cap >= 5, slots 5-9 with cap >= 10; all
    summed over an in-process group's shards; all 0 on sparse rows).  Test surface.

@@ -1009,7 +1009,10 @@ class Sim:
         self.lib.call("sim_reset_kernel_time", self.h)
 
     def debug_paths(self) -> int:
-        """OR of the kernel-variant bits (PATH_* of kb_common.h) that did work; 0 for the oracle."""
+        """OR of the kernel-variant bits (PATH_* of kb_common.h) that did work; 0 for the oracle.  Bits 1..512:
+        the wide-row variants and wave 0's deferred pass; 1024..8192: the paths chosen by list lengths (row pass
+        with HBM lists, KPR proof on a wrapped log ring, > 1024 new joiners in k_resp_node, a Join response
+        past the union slots crossing shards as a list)."""
         if "sim_debug_paths" not in self.lib.fn:
             return 0
         v = C.c_uint32()

@@ -50,7 +50,12 @@ enum CtrIdx {
 enum : uint32_t { PATH_PHASEB_HBM = 1, PATH_RESP_SCRATCH_SAMPLED = 2, PATH_RESP_SCRATCH_FULL = 4, PATH_KP_BIG_HBM = 8,
                   PATH_PROC_UNSORTED = 16, PATH_BFAIL_PREP_HBM = 32, PATH_RESP_WAVE = 64, PATH_KP_BIG_LDS = 128,
                   PATH_RESP_WAVE_HBM = 256,
-                  PATH_PROC_DEFERRED = 512 };   // split wave 0: the deferred k_proc pass handled a BIG destination's inbox
+                  PATH_PROC_DEFERRED = 512,     // split wave 0: the deferred k_proc pass handled a BIG destination's inbox
+                  // the mass-join paths: list lengths past the LDS caps, a wrapped log ring (tests/massjoin.py)
+                  PATH_ROWPASS_LDS_HBM_LISTS = 1024,   // row pass k_rowpass<true,false>: rows staged, lists from HBM (host-set)
+                  PATH_KPR_WRAPPED = 2048,             // a KPR reply proven oversize from a wrapped log ring
+                  PATH_RESP_JOINERS_HBM = 4096,        // k_resp_node served a receiver with nnew > RESP_JCAP
+                  PATH_JOIN_LIST_PAST_UCAP = 8192 };   // row shards: a Join response to a joiner past UCAP crossed as a list
 constexpr int NSEG = 64;          // fingerprint checkpoints per row
 constexpr int ZT = 9;             // LDS nibble tables for Z^0..Z^8
 constexpr int ZB = 9 * 1024;      // byte tables for Z^0..Z^8 (4 lookups per multiply)

@@ -1567,6 +1567,7 @@ __global__ __launch_bounds__(256) void k_resp_node(Dev d, PhaseB pb, const uint3
           ob.msgs[ob.off[i] + q] = m;
           if (nk != expect) set_err(d, DERR_RESP);
           if (gscratch) path_hit(d, sample ? PATH_RESP_SCRATCH_SAMPLED : PATH_RESP_SCRATCH_FULL);
+          if (!jl) path_hit(d, PATH_RESP_JOINERS_HBM);
         }
         poff += cap; q++;
         __syncthreads();

@@ -381,6 +381,7 @@ struct kb_sim {
   BCast* bfail_loc; BCast* bjoin_loc;  // sharded: this shard's part, before the all-gather
   uint32_t nf, nj;
   uint32_t ucap = 0;                   // Join-response union slots (sharded meshes, kb_waves.h UCAP)
+  uint32_t host_paths = 0;             // PATH_* bits of variants chosen at a launch (kb_sim_debug_paths ORs them in)
   uint64_t xbytes_cross = 0, xbytes_all = 0;   // bytes this shard's waves sent to other shards / to every shard
   BcastSlots bs;
   uint32_t* join_off; uint32_t* fail_off;
@@ -735,7 +736,7 @@ constexpr uint32_t KB_FOLD_WAVES = 16384;                            // fold wav
   if (xf) {
     XState& x = s->xs;
     x.world = (uint32_t)world; x.R = R; x.S = rows_per; x.RS = R + 1;
-    x.NWW = d.NWR; x.nju = 0; x.uon = 0;
+    x.NWW = d.NWR; x.nju = 0; x.nj = 0; x.uon = 0;
     s->ucap = std::min<uint32_t>(UCAP, C);             // Join-response unions (kb_waves.h): slots and their reserve
     A(x.ostatus, s->msg_cap); A(x.xcnt, (size_t)world * x.RS); A(x.xpay, (size_t)world * x.RS);
     A(x.xoff, (size_t)world * x.RS); A(x.xpoff, (size_t)world * x.RS); A(x.xb, 2 * world);
@@ -1121,6 +1122,7 @@ static int launch_waves(kb_sim* s, int32_t rk) {
       // wave 0: the round's joiners' slots for the Join-response unions
       s->xs.nju = w == 0 && !last ? std::min<uint32_t>(s->nj, s->ucap) : 0u;
       s->xs.uon = s->xs.nju && !(d.dbg & KB_DBG_NO_UNION) ? 1u : 0u;
+      s->xs.nj = s->xs.uon ? s->nj : 0u;
       s->xs.bjoin = s->bjoin;
       if (s->xs.uon) klaunch(s, KI_ROUTE_X, k_union_slots, dim3((s->xs.nju + 255) / 256), dim3(256), 0, s->xs);
       klaunch(s, KI_ROUTE_X, k_route_x, dim3(gnode), dim3(tb), 0, d, ob, s->xs, r, w, last);
@@ -1410,6 +1412,7 @@ static int step_round(kb_sim* s) {
               lds, per_cu, (size_t)s->lds_per_cu, blocks);
     const bool rp_prof = s->debug_waves && (d.dev & 2048);
     if (rp_prof) HIPCHK(hipMemsetAsync(d.ctr + C_DBG_TNODE, 0, 4 * (C_DBG_MSGS - C_DBG_TNODE), st));
+    if (ldsb && !ll) s->host_paths |= PATH_ROWPASS_LDS_HBM_LISTS;   // coverage (test surface), with the device's bits
     if (ldsb && ll) klaunch(s, KI_ROWPASS, k_rowpass<true, true>, dim3(blocks), dim3(64 * wpb), (uint32_t)lds, d, pb, s->ro, r);
     else if (ldsb) klaunch(s, KI_ROWPASS, k_rowpass<true, false>, dim3(blocks), dim3(64 * wpb), (uint32_t)lds, d, pb, s->ro, r);
     else if (ll) klaunch(s, KI_ROWPASS, k_rowpass<false, true>, dim3(blocks), dim3(64 * wpb), (uint32_t)lds, d, pb, s->ro, r);
@@ -2120,6 +2123,7 @@ extern "C" int kb_sim_host_syncs(kb_sim* s, uint64_t* n) {
 // OR of the PATH_* bits (kb_common.h) of the kernel variants that did work since creation (none on the sparse rows)
 static int eng_debug_paths(kb_sim* s, uint32_t* mask) {
   HIPCHK(hipMemcpy(mask, s->d.ctr + C_PATHS, 4, hipMemcpyDeviceToHost));
+  *mask |= s->host_paths;
   return KB_OK;
 }
 static int eng_debug_paths(SpSim*, uint32_t* mask) { *mask = 0; return KB_OK; }

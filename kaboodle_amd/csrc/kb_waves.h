@@ -172,7 +172,10 @@ __device__ __attribute__((always_inline)) inline void kpr_probe(const Dev& d, co
       }
       total += wave_sum(c);
     }
-    if (total > d.capk + 1 && l == 0) d.kpr_big[i] = r;
+    if (total > d.capk + 1 && l == 0) {
+      d.kpr_big[i] = r;
+      if (fn - ws > LOGCAP) path_hit(d, PATH_KPR_WRAPPED);   // proven from the newest LOGCAP entries of a wrapped ring
+    }
   }
 }
 
@@ -244,6 +247,7 @@ struct XState {
   // whether this shard delivered anything to the slot's joiner; bjoin = the round's Join list (slot = entry)
   uint32_t* jslot; uint32_t* ubits; uint32_t* uany; const BCast* bjoin;
   uint32_t nju, NWW, uon;           // slots in use, words per bitmap, unions on (wave 0 of a round with joiners)
+  uint32_t nj;                      // the round's joiners (wave 0); those past slot nju get their responses as lists
 };
 // the union slot a delivered record's ids go to, or ~0 (they travel with the record)
 __device__ inline uint32_t x_union_slot(const XState& x, const Msg& m) {
@@ -287,7 +291,14 @@ __global__ __launch_bounds__(256) void k_route_x(Dev d, OutBuf ob, XState x, int
       atomicAdd(&x.xcnt[slot], 1u);
       const uint32_t e = x_union_slot(x, m);
       if (e != 0xFFFFFFFFu) x.uany[e] = 1u;                           // its ids go to the joiner's union
-      else if (m.kind == K_KP && m.a) atomicAdd(&x.xpay[slot], m.a);
+      else if (m.kind == K_KP && m.a) {
+        atomicAdd(&x.xpay[slot], m.a);
+        // coverage (test surface): a Join response to a joiner past the union slots leaves this shard as a list
+        if (x.uon && x.nj > x.nju && m.dest / x.S != d.lo / x.S &&
+            !(__hip_atomic_load(&d.ctr[C_PATHS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & PATH_JOIN_LIST_PAST_UCAP))
+          for (uint32_t f = x.nju; f < x.nj; ++f)
+            if (x.bjoin[f].sender == m.dest) { path_hit(d, PATH_JOIN_LIST_PAST_UCAP); break; }
+      }
     }
     if (!last) x.ostatus[g] = st;
   }
@@ -1440,6 +1451,7 @@ void k_proc(Dev d, OutBuf ib, OutBuf ob, WaveCtl wc, int32_t r_arg, const uint32
               take(ok, j);
             }
           }
+          if (!complete && over && l == 0) path_hit(d, PATH_KPR_WRAPPED);   // proven oversize from a wrapped ring
           if (!complete && !over) {                   // rare: rescan the row itself
             total = 0;
             size = 8 + (d.seglen[i] - ADDR_LEN) + 4 + 8;
