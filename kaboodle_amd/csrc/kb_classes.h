@@ -364,7 +364,8 @@ extern "C" int kb_sim_fp_classes(kb_sim* s, kb_fp_classes* out, kb_fp_class* lis
   { const int rc = kb_sim_true_fingerprint(s, &tfp); if (rc) return rc; }
   FcPlan p;
   if (!fc_plan(s->C, p)) { seterr("kb_sim_fp_classes: capacity above 2^30"); return KB_CAPACITY; }
-  { const int rc = dev_reserve(&s->fc_buf, &s->fc_cap, p.bytes, "fp_classes: scratch allocation failed"); if (rc) return rc; }
+  // the scratch belongs to the engine whose stream runs the census (it is released with that engine)
+  { const int rc = route(s, R_FIRST, 0, [&](auto* e) { return eng_grow(e, &s->fc_buf, &s->fc_cap, p.bytes); }); if (rc) return rc; }
   std::vector<FcSeg> segs;
   if (grp) route(s, R_ALL, 0, [&](auto* e) { segs.push_back(FcSeg{eng_fp(e) + e->lo, e->lo, e->R}); return KB_OK; });
   // the first shard's stream runs the census; every shard is on its device

@@ -270,8 +270,8 @@ extern "C" int kb_sim_reciprocity(kb_sim* s, kb_reciprocity* out, uint32_t* mutu
   // the pair list: a device buffer and a host vector for exactly the known total (8 bytes each per pair), grown when
   // a later call needs more; the total is at most cap_pairs, so the caller's own 8 * cap_pairs buffer bounds both
   const uint64_t np = out->mutual_pairs;
-  { const int rc = dev_reserve(&h->rc_pairs, &h->rc_pairs_cap, 8ull * np, "reciprocity: pair buffer allocation failed"); if (rc) return rc; }
-  a.pairs = static_cast<uint2*>(h->rc_pairs); a.cap = np;
+  { const int rc = eng_grow(h, &h->rc_pairs, &h->rc_pairs_cap, (size_t)np); if (rc) return rc; }
+  a.pairs = h->rc_pairs; a.cap = np;
   CsTimer tp;
   if (!tp.start(h->st)) { seterr("reciprocity: events"); return KB_IO_ERROR; }
   k_rc_pairs<<<dim3(nb, nb), RC_THREADS, 0, h->st>>>(a);

@@ -395,9 +395,9 @@ struct kb_sim {
   uint32_t* w0ctr = nullptr;           // its counters (W0_*: deferred nodes, k_proc's tickets)
   uint16_t* lat_col;                   // [C] one node's latencies (peer_states), track_latency only
   uint32_t* fnamed;                    // [NWR] peers named by the round's Failed list (track_latency only)
-  uint32_t* resp_scratch; size_t resp_scratch_words;
+  uint32_t* resp_scratch; size_t resp_scratch_words;   // k_resp_node's HBM scratch, grown on demand
   RowOut ro;
-  Event* d_events; uint32_t events_cap;
+  Event* d_events; size_t events_cap;
   // sharded waves: send side (xs), all-gathered counts, receive buffers (grown on demand)
   XState xs;
   uint32_t* xall; unsigned long long* xstats;
@@ -424,8 +424,9 @@ struct kb_sim {
   uint32_t ncu = 256;
   uint32_t* cs_buf = nullptr;          // the census's scratch (kb_census.h), allocated by the first census
   uint32_t* rc_buf = nullptr;          // the reciprocity census's scratch (kb_recip.h), allocated by its first call
-  void* rc_pairs = nullptr; size_t rc_pairs_cap = 0;   // its pair list, bytes; grown on demand
-  void* fc_buf = nullptr; size_t fc_cap = 0;   // the class census's scratch (kb_classes.h), bytes; grown on demand
+  uint2* rc_pairs = nullptr; size_t rc_pairs_cap = 0;  // its pair list, grown on demand
+  char* fc_buf = nullptr; size_t fc_cap = 0;   // the class census's scratch (kb_classes.h), bytes; grown on demand, held by
+                                               // the engine whose stream runs the census (a group's first shard)
   double census_ms[CM_N] = {};         // device time of the last census of each kind, on the handle that was asked
   bool debug_waves = false;
   size_t lds_per_cu = 65536;
@@ -461,6 +462,8 @@ template <class T> static hipError_t talloc(kb_sim* s, T** p, size_t n) {
   if (e == hipSuccess) s->allocs.push_back((void*)*p);
   return e;
 }
+template <class T> static hipError_t eng_alloc(kb_sim* s, T** p, size_t n) { return talloc(s, p, n); }   // kb_roundframe.h's hooks
+static const char* eng_alloc_what(kb_sim*) { return "device allocation failed: "; }
 template <class T> static T* bias(T* base, size_t per_row, uint32_t lo) {
   return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) - sizeof(T) * per_row * lo);
 }
@@ -598,6 +601,7 @@ static int upload_segments(kb_sim* s) {
   return KB_OK;
 }
 
+#include "kb_roundframe.h"
 #include "kb_sparse_host.h"
 
 // a handle answered by the sparse-row engine: the whole mesh (xf null) or one row shard of it (owns xf)
@@ -617,9 +621,6 @@ static int sp_wrap(const kb_config* cfg, int rank, int world, Xfer* xf, kb_sim**
 static void free_all(kb_sim* s) {
   for (void* p : s->allocs) (void)hipFree(p);
   s->allocs.clear();
-  void* dyn[] = {s->newmask_base, s->respmask_base, s->resp_scratch, s->d_events, s->rmsg, s->rpay, s->rstatus,
-                 s->rinbox, s->rkp, s->d_presp, s->d_presp_n, s->rpack, s->rpack_in, s->d_inj, s->d_inj_ids, s->rc_pairs};
-  for (void* p : dyn) if (p) (void)hipFree(p);
 }
 static void destroy_shard(kb_sim* s) {
   (void)hipSetDevice(s->device);
@@ -897,7 +898,6 @@ extern "C" int kb_sim_create_local(const kb_config* cfg, int32_t shards, kb_sim*
 
 extern "C" int kb_sim_destroy(kb_sim* s) {
   if (!s) return KB_INVALID_ARGUMENT;
-  if (s->fc_buf) { (void)hipSetDevice(s->device); (void)hipFree(s->fc_buf); s->fc_buf = nullptr; }
   if (!is_group(s)) { destroy_one(s); return KB_OK; }
   for (kb_sim* t : s->shards) destroy_one(t);
   delete s->hub;
@@ -944,74 +944,52 @@ static int err_status(uint32_t e) {
   }
   return KB_OK;
 }
-// replace a tracked device allocation by a larger one (contents are not kept)
-template <class T> static hipError_t regrow(kb_sim* s, T** p, size_t n) {
-  for (auto& q : s->allocs) if (q == (void*)*p) { (void)hipFree(q); q = nullptr; }
-  s->allocs.erase(std::remove(s->allocs.begin(), s->allocs.end(), nullptr), s->allocs.end());
-  *p = nullptr;
-  return talloc(s, p, n);
-}
 // The wave-0 outbox holds the round's Join responses (src/kaboodle.rs:356-392), whose volume follows the
 // mesh's dynamics (≈1 % of the members answer each joiner with up to 567 ids): when the scanned totals
 // exceed it, it grows, with the buffers indexed by its slots (record status, inbox lists, send side).
+// The outbox's own two buffers grow under o0.pay_cap / o0.msg_cap; the buffers that must cover it (the send side's
+// payload; the slot-indexed ones) are groups under pay_cap / msg_cap and follow whenever the outbox is the larger.
 static int grow_wave0(kb_sim* s, size_t need_msg, size_t need_pay) {
   OutBuf& o0 = s->ob[0];
-  s->buf_gen++;                                    // the captured receive window holds the old buffers
+  window_stale(s);
   const size_t lim = 0xF0000000ull;
   if (need_pay > o0.pay_cap) {
     const size_t cap = std::min(lim, need_pay + need_pay / 4);
     if (cap < need_pay) { seterr("Join-response payload beyond 2^32 ids"); return KB_CAPACITY; }
-    HIPCHK(regrow(s, &o0.pay, cap));
-    o0.pay_cap = (uint32_t)cap;
-    if (s->xf && cap > s->pay_cap) { HIPCHK(regrow(s, &s->xs.spay, cap + (size_t)s->ucap * s->xs.NWW)); s->pay_cap = (uint32_t)cap; }
+    const int rc = eng_grow(s, &o0.pay, &o0.pay_cap, cap);
+    if (rc) return rc;
+  }
+  if (s->xf && o0.pay_cap > s->pay_cap) {
+    const size_t cap = o0.pay_cap;
+    const int rc = eng_grow_group(s, &s->pay_cap, cap, cap + (size_t)s->ucap * s->xs.NWW, &s->xs.spay);
+    if (rc) return rc;
   }
   if (need_msg > o0.msg_cap) {
     const size_t cap = std::min(lim, need_msg + need_msg / 4);
     if (cap < need_msg) { seterr("wave-0 records beyond 2^32"); return KB_CAPACITY; }
-    HIPCHK(regrow(s, &o0.msgs, cap));
-    o0.msg_cap = (uint32_t)cap;
-    if (cap > s->msg_cap) {                  // slot-indexed buffers cover the larger outbox
-      if (!s->xf) { HIPCHK(regrow(s, &s->wc.status, cap)); HIPCHK(regrow(s, &s->wc.inbox, cap)); HIPCHK(regrow(s, &s->wc.kin, cap)); }
-      else { HIPCHK(regrow(s, &s->xs.ostatus, cap)); HIPCHK(regrow(s, &s->xs.smsg, cap + s->ucap)); }
-      s->msg_cap = (uint32_t)cap;
-    }
+    const int rc = eng_grow(s, &o0.msgs, &o0.msg_cap, cap);
+    if (rc) return rc;
+  }
+  if (o0.msg_cap > s->msg_cap) {               // slot-indexed buffers cover the larger outbox
+    const size_t cap = o0.msg_cap;
+    // (sharded: the send side keeps the union slots' reserve past the outbox; the status bytes get it too, unused)
+    const int rc = !s->xf ? eng_grow_group(s, &s->msg_cap, cap, cap, &s->wc.status, &s->wc.inbox, &s->wc.kin)
+                          : eng_grow_group(s, &s->msg_cap, cap, cap + s->ucap, &s->xs.ostatus, &s->xs.smsg);
+    if (rc) return rc;
   }
   return KB_OK;
 }
 
-// External peers' export buffers hold every record a round routes to them.  A real instance's Join
-// (kb_sim_inject KB_WIRE_JOIN) draws KnownPeers responses from ~1 % of the running peers, capj ids each
-// (src/kaboodle.rs:284-304, :356-392): so before the window the buffers grow to the wave-0 totals (all Join
-// responses and injected payloads, an upper bound of what wave 0 can export) plus a fixed allowance for the
-// later waves' replies.  They are empty at a round's start (drained after every round), so nothing is copied.
-constexpr uint32_t XREC_MIN = 1u << 16, XIDS_MIN = 1u << 22;
-static int size_exports(kb_sim* s, uint64_t recs, uint64_t ids) {
-  const uint64_t nr = recs + XREC_MIN, ni = ids + XIDS_MIN;
-  if (nr > 0xFFFFFFFFull || ni > 0xFFFFFFFFull) { seterr("export buffer beyond 2^32 entries"); return KB_CAPACITY; }
-  if (nr > s->d.xrec_cap) { HIPCHK(regrow(s, &s->d.xrec, nr + nr / 4)); s->d.xrec_cap = (uint32_t)std::min<uint64_t>(nr + nr / 4, 0xFFFFFFFFull); s->buf_gen++; }
-  if (ni > s->d.xids_cap) { HIPCHK(regrow(s, &s->d.xids, ni + ni / 4)); s->d.xids_cap = (uint32_t)std::min<uint64_t>(ni + ni / 4, 0xFFFFFFFFull); s->buf_gen++; }
-  return KB_OK;
-}
-
-// grow the receive side of the sharded waves to hold nm records and np payload ids
+// grow the receive side of the sharded waves to hold nm records and np payload ids (rmsg_cap covers the records
+// and the three buffers their slots index)
 static int ensure_recv(kb_sim* s, size_t nm, size_t np) {
   if (nm > s->rmsg_cap || !s->rmsg) {
-    void* old[] = {s->rmsg, s->rstatus, s->rinbox, s->rkp};
-    for (void* p : old) if (p) (void)hipFree(p);
-    s->rmsg = nullptr; s->rstatus = nullptr; s->rinbox = nullptr; s->rkp = nullptr;
     const size_t cap = std::max<size_t>(nm + nm / 2, 1u << 16);
-    HIPCHK(hipMalloc(&s->rmsg, sizeof(Msg) * cap)); HIPCHK(hipMalloc(&s->rstatus, cap));
-    HIPCHK(hipMalloc(&s->rinbox, 4 * cap)); HIPCHK(hipMalloc(&s->rkp, 4 * cap));
-    s->rmsg_cap = cap;
+    const int rc = eng_grow_group(s, &s->rmsg_cap, cap, cap, &s->rmsg, &s->rstatus, &s->rinbox, &s->rkp);
     s->wc.status = s->rstatus; s->wc.inbox = s->rinbox; s->wc.kin = s->rkp;
+    if (rc) return rc;
   }
-  if (np > s->rpay_cap || !s->rpay) {
-    if (s->rpay) (void)hipFree(s->rpay);
-    s->rpay = nullptr;
-    const size_t cap = std::max<size_t>(np + np / 2, 1u << 20);
-    HIPCHK(hipMalloc(&s->rpay, 4 * cap));
-    s->rpay_cap = cap;
-  }
+  if (np > s->rpay_cap || !s->rpay) return eng_grow(s, &s->rpay, &s->rpay_cap, std::max<size_t>(np + np / 2, 1u << 20));
   return KB_OK;
 }
 
@@ -1095,6 +1073,11 @@ static int gather_broadcasts(kb_sim* s, uint32_t* err) {
   return KB_OK;
 }
 
+// what the row pass launches with (rowpass_plan, below): both broadcast lists staged in LDS (ll), each row's bitset
+// staged (ldsb), waves per workgroup, dynamic LDS bytes, resident workgroups per CU, workgroups
+struct RowPlan { bool ldsb, ll; uint32_t wpb; size_t lds; uint32_t per_cu, blocks; };
+#include "kb_rounddbg.h"
+
 // The receive window's delivery waves.  rk is the round the kernels take as
 // argument; rk < 0 makes them read it from the device (d.ctr[C_ROUND], set by k_log_mark), which lets
 // the unsharded window be captured once as a HIP graph and replayed every round.
@@ -1147,25 +1130,14 @@ static int launch_waves(kb_sim* s, int32_t rk) {
       a.list = s->wc.active; a.list_count = d.ctr + C_ACTIVE; a.list_base = s->lo; a.list_or3 = 1;
       launch_scan(s, a);
     }
-    if (s->debug_waves) {                               // KB_DEBUG_WAVES: inbox sizes per wave
-      std::vector<uint32_t> c1(R);
-      HIPCHK(hipMemcpyAsync(c1.data(), L(s, s->wc.cnt1), 4ull * R, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      uint64_t sum = 0; uint32_t mx = 0, arg = 0, big = 0;
-      for (uint32_t k = 0; k < R; ++k) { sum += c1[k]; if (c1[k] > mx) { mx = c1[k]; arg = s->lo + k; } big += c1[k] > 64; }
-      fprintf(stderr, "[kb] round %d wave %u: in-order msgs %llu, max inbox %u (node %u), inboxes > 64: %u\n", r, w,
-              (unsigned long long)sum, mx, arg, big);
-    }
+    { const int rc = dbg_wave_inboxes(s, r, w); if (rc) return rc; }
     // (the inbox placement, and in PROBE_GROUPS more workgroups the KPR oversize probe)
     if (!s->xf) klaunch(s, KI_SCATTER, k_scatter, dim3(gnode + PROBE_GROUPS), dim3(tb), 0, d, ob, s->wc, r, gnode);
     else if (nrecv) {
       const uint32_t nsc = (nrecv + 255) / 256;
       klaunch(s, KI_SCATTER_FLAT, k_scatter_flat, dim3(nsc + PROBE_GROUPS), dim3(256), 0, d, ib, s->wc, nrecv, r, nsc);
     }
-    if (s->debug_waves) {
-      HIPCHK(hipMemsetAsync(d.ctr + C_DBG_INS, 0, 52, st));
-      HIPCHK(hipMemsetAsync(d.ctr + C_DBG_SLOW_LONG, 0, 20, st));
-    }
+    { const int rc = dbg_proc_clear(s); if (rc) return rc; }
     // wave 0 of a round with joiners: their BIG groups overlap the in-order handlers of every other node.  Not
     // under graph capture (the window stays one chain there), KB_DEBUG_WAVES (its read-backs follow st only) or
     // KB_DBG_WAVE0_SERIAL
@@ -1204,29 +1176,7 @@ static int launch_waves(kb_sim* s, int32_t rk) {
       klaunch(s, KI_PROC, k_proc, dim3(std::min<uint32_t>(2 * s->ncu, std::max<uint32_t>(1u, (s->nj + 3) / 4))), dim3(256), 0, d, ib, nb,
               s->wc, r, (const uint32_t*)s->defer, (const uint32_t*)(s->w0ctr + W0_DEFER), (uint32_t*)nullptr);
     }
-    if (s->debug_waves) {
-      uint32_t dbg[13], slow = 0;
-      HIPCHK(hipMemcpyAsync(dbg, d.ctr + C_DBG_INS, 52, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(&slow, d.ctr + C_SLOW, 4, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      fprintf(stderr, "[kb] round %d wave %u: k_proc nodes %u, prologue inserts %u, fingerprint refreshes %u (max per "
-              "node %u), KPR scans %u (log entries %u), incremental bases %u\n", r, w, slow, dbg[0], dbg[1], dbg[2], dbg[3],
-              dbg[4], dbg[5]);
-      if (d.dev & 256) {
-        uint32_t why[5];
-        HIPCHK(hipMemcpy(why, d.ctr + C_DBG_SLOW_LONG, 20, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[kb] round %d wave %u: to k_proc because inbox > %u: %u, sender not a member: %u, fingerprint stale: %u, "
-                "KPR not proven oversize: %u, other: %u\n", r, w, FAST_MAX, why[0], why[1], why[2], why[3], why[4]);
-      }
-      if (d.dev & 128)
-        fprintf(stderr, "[kb] round %d wave %u: k_kp_group BIG workgroup-destinations %u, messages %u: stage+arms %.1f us, "
-                "prologues %.1f, write-back+refold %.1f (sums), max total %.1f\n", r, w, dbg[10], dbg[12], dbg[6] * 0.01,
-                dbg[8] * 0.01, dbg[9] * 0.01, dbg[7] * 0.01);
-      if (d.dev & 64)
-        fprintf(stderr, "[kb] round %d wave %u: k_proc node time sum %.1f us (max %.1f), take_base %.1f, insertions %.1f, "
-                "start %.1f, end %.1f, messages %u\n", r, w, dbg[6] * 0.01, dbg[7] * 0.01, dbg[8] * 0.01, dbg[9] * 0.01,
-                dbg[10] * 0.01, dbg[11] * 0.01, dbg[12]);
-    }
+    { const int rc = dbg_proc_report(s, r, w); if (rc) return rc; }
     cur ^= 1;
   }
   s->cur_wave = -1;
@@ -1242,8 +1192,8 @@ static int launch_waves(kb_sim* s, int32_t rk) {
 static int move_row(kb_sim* s, uint32_t from, uint32_t to, bool* snap_after) {
   *snap_after = false;
   const RowPack LP = row_pack_layout(s->W, s->d.NWR, s->d.lat != nullptr, s->d.tst != nullptr);
-  if (!s->rpack) HIPCHK(hipMalloc(&s->rpack, 4ull * LP.words));
-  if (s->xf && !s->rpack_in) HIPCHK(hipMalloc(&s->rpack_in, 4ull * LP.words));
+  if (!s->rpack) { size_t c = 0; const int rc = eng_grow(s, &s->rpack, &c, LP.words); if (rc) return rc; }
+  if (s->xf && !s->rpack_in) { size_t c = 0; const int rc = eng_grow(s, &s->rpack_in, &c, LP.words); if (rc) return rc; }
   const bool have = from >= s->lo && from < s->hi, take = to >= s->lo && to < s->hi;
   size_t wk = 0;
   while (wk < s->watch_node.size() && s->watch_node[wk] != from) ++wk;
@@ -1287,76 +1237,118 @@ static int move_row(kb_sim* s, uint32_t from, uint32_t to, bool* snap_after) {
   return KB_OK;
 }
 
-static int step_round(kb_sim* s) {
+// ---- one round, as its phases ---------------------------------------------------------------
+// What the phases hand on.  Everything here is launches on st (side work on st2, forked and joined by events) in
+// one fixed order; the host waits only where a phase says so.
+struct Round {
+  int32_t r;
+  PhaseB pb;                                         // the broadcast phase's lists, masks and per-row sums
+  bool lat_fail = false;                             // latency upkeep for Failed removals runs this round (side work 1)
+  uint32_t np = 0;                                   // Probes delivered this round
+  uint32_t ninj = 0; bool inj_pay = false;           // records injected by external peers; they carry payload ids
+  hipEvent_t er[2] = {nullptr, nullptr};             // the whole round, read back next round
+  size_t krec0 = 0;                                  // profile records of earlier rounds (complete)
+};
+constexpr uint32_t TB = 256;                         // threads of the per-node launches
+static uint32_t gnode(const kb_sim* s) { return (s->R + TB - 1) / TB; }
+
+// API events in call order; a restart first moves the instance's map to its new address (the events before it
+// have been applied: its stop removed the old self), then starts it there.  One host wait.
+static int apply_events(kb_sim* s, int32_t r) {
   Dev& d = s->d;
-  const int32_t r = s->round;
-  const uint32_t C = s->C, R = s->R;
-  hipStream_t st = s->st;
-  const uint32_t tb = 256, gnode = (R + tb - 1) / tb, gwave = (R + 3) / 4, gall = (C + tb - 1) / tb;
-  const size_t krec0 = s->krec.size();               // records of earlier rounds (complete)
-  s->cur_wave = -1;
-  hipEvent_t er[2] = {nullptr, nullptr};              // the whole round, read back next round
-  for (int k = 0; k < 2; ++k) {
-    if (!s->ev_free.empty()) { er[k] = s->ev_free.back(); s->ev_free.pop_back(); }
-    else (void)hipEventCreate(&er[k]);
-  }
-  (void)hipEventRecord(er[0], st);
-  // 0. stamp window
-  if (r > 0 && r % EPOCH == 0) klaunch(s, KI_REBASE, k_rebase, dim3(8192), dim3(256), 0, d, r);
-  // 1. lifecycle (every shard applies the same events and churn draws to the replicated per-id state)
-  if (!s->events.empty()) {
-    if (s->events.size() > s->events_cap) {
-      if (s->d_events) (void)hipFree(s->d_events);
-      s->events_cap = (uint32_t)s->events.size() * 2;
-      HIPCHK(hipMalloc(&s->d_events, sizeof(Event) * s->events_cap));
-    }
-    HIPCHK(hipMemcpyAsync(s->d_events, s->events.data(), sizeof(Event) * s->events.size(), hipMemcpyHostToDevice, st));
-    // in call order; a restart first moves the instance's map to its new address (the events before it
-    // have been applied: its stop removed the old self), then starts it there
-    size_t k0 = 0;
-    for (size_t k = 0; k <= s->events.size(); ++k) {
-      const bool rs = k < s->events.size() && s->events[k].kind == EV_RESTART;
-      if (k == s->events.size() || rs) {
-        if (k > k0) klaunch(s, KI_EVENTS, k_events, dim3(1), dim3(1), 0, d, s->d_events + k0, (uint32_t)(k - k0), r);
-        k0 = k;
-        if (rs) {
-          bool snap_after = false;
-          const uint32_t to = s->events[k].node;
-          const int rc = move_row(s, s->events[k].src, to, &snap_after);
-          if (rc) return rc;
-          if (snap_after) {                                // the restart itself, then the observer's starting point
-            klaunch(s, KI_EVENTS, k_events, dim3(1), dim3(1), 0, d, s->d_events + k, 1u, r);
-            size_t kt = 0;
-            while (s->watch_node[kt] != to) ++kt;
-            k_events_commit<<<(d.NWR + 255) / 256, 256, 0, st>>>(d.bits + (size_t)to * d.NWR, s->watch_snap[kt], d.NWR);
-            k0 = k + 1;
-          }
+  if (s->events.empty()) return KB_OK;
+  { const int rc = round_upload_events(s); if (rc) return rc; }
+  size_t k0 = 0;
+  for (size_t k = 0; k <= s->events.size(); ++k) {
+    const bool rs = k < s->events.size() && s->events[k].kind == EV_RESTART;
+    if (k == s->events.size() || rs) {
+      if (k > k0) klaunch(s, KI_EVENTS, k_events, dim3(1), dim3(1), 0, d, s->d_events + k0, (uint32_t)(k - k0), r);
+      k0 = k;
+      if (rs) {
+        bool snap_after = false;
+        const uint32_t to = s->events[k].node;
+        const int rc = move_row(s, s->events[k].src, to, &snap_after);
+        if (rc) return rc;
+        if (snap_after) {                                // the restart itself, then the observer's starting point
+          klaunch(s, KI_EVENTS, k_events, dim3(1), dim3(1), 0, d, s->d_events + k, 1u, r);
+          size_t kt = 0;
+          while (s->watch_node[kt] != to) ++kt;
+          k_events_commit<<<(d.NWR + 255) / 256, 256, 0, s->st>>>(d.bits + (size_t)to * d.NWR, s->watch_snap[kt], d.NWR);
+          k0 = k + 1;
         }
       }
     }
-    HIPCHK(sync_st(s));
-    s->events.clear();
   }
+  HIPCHK(sync_st(s));
+  s->events.clear();
+  return KB_OK;
+}
+// 0. stamp window; 1. lifecycle (every shard applies the same events and churn draws to the replicated per-id state)
+static int round_lifecycle(kb_sim* s, Round& q) {
+  Dev& d = s->d;
+  const int32_t r = q.r;
+  if (r > 0 && r % EPOCH == 0) klaunch(s, KI_REBASE, k_rebase, dim3(8192), dim3(256), 0, d, r);
+  { const int rc = apply_events(s, r); if (rc) return rc; }
   const bool faults_on = s->cfg.fault_end_round < 0 || r < s->cfg.fault_end_round;
   if (faults_on && s->cfg.churn_threshold) {
-    klaunch(s, KI_CHURN_LEAVE, k_churn_leave, dim3(gall), dim3(tb), 0, d, r);
+    klaunch(s, KI_CHURN_LEAVE, k_churn_leave, dim3((s->C + TB - 1) / TB), dim3(TB), 0, d, r);
     klaunch(s, KI_CHURN_JOIN, k_churn_join, dim3(1), dim3(64), 0, d, r);
   }
-  klaunch(s, KI_LOG_MARK, k_log_mark, dim3(gnode), dim3(tb), 0, d, r);
-  // 2. broadcasts of round r-1 (with the external peers' Joins)
-  if (!s->inj_join.empty()) { const int rc = merge_ext_joins(st, s->bjoin, &s->nj, s->inj_join, 0, C); if (rc) return rc; }
-  OutBuf& o0 = s->ob[0];
-  PhaseB pb;
+  klaunch(s, KI_LOG_MARK, k_log_mark, dim3(gnode(s)), dim3(TB), 0, d, r);
+  return KB_OK;
+}
+
+// The row pass's launch shape (broadcast phase + A3 candidates, persistent waves; the broadcast lists staged in LDS
+// once per workgroup when they fit).  The occupancy query runs once per shape (occ_key / occ_val).
+// the four instantiations, named once: f(kernel) for the one the plan chose
+template <class F> static void rowpass_with(const RowPlan& p, F&& f) {
+  if (p.ldsb) { if (p.ll) f(k_rowpass<true, true>); else f(k_rowpass<true, false>); }
+  else if (p.ll) f(k_rowpass<false, true>);
+  else f(k_rowpass<false, false>);
+}
+static RowPlan rowpass_plan(kb_sim* s, bool pb_hbm) {
+  const Dev& d = s->d;
+  RowPlan p;
+  const uint32_t budget = RP_LDS_BYTES / 4;          // dynamic LDS words per workgroup
+  p.ll = s->nf <= PB_FMAX && s->nj <= PB_JMAX;       // both broadcast lists staged in LDS
+  uint32_t listw = p.ll ? 2 * s->nf + s->nj : 0;
+  if (listw > budget / 2 || pb_hbm) { p.ll = false; listw = 0; }
+  // the LDS variant stages each row's whole bitset for the Failed group's membership tests; without a
+  // Failed list (quiet rounds: A3 and a few Joins only) the row is read where A3 and the Joins touch it
+  // (372K peers, no broadcasts: 3.41 -> 0.54 ms, profiles/r04e_rowpass_variants.json).  (Rows too wide for
+  // more than 1-3 staged bitsets per workgroup still stage: the in-place variant with 8 waves per workgroup
+  // and the lists in LDS measured 17.4 -> 21.5 ms at 262K peers and 44.7 -> 41.8 ms at 372K in rounds with
+  // Failed lists, its random membership reads missing L2, profiles/r04s_nsweep.json)
+  p.ldsb = s->W <= PB_LDS_W && budget - listw >= d.NWR && !pb_hbm && s->nf > 0;
+  p.wpb = p.ldsb ? std::min<uint32_t>(RP_WAVES, (budget - listw) / d.NWR) : RP_WAVES;
+  p.lds = 4ull * ((p.ldsb ? (size_t)p.wpb * d.NWR : 0) + listw);
+  int occ = 0;                                       // resident workgroups per CU (LDS, registers)
+  const uint64_t okey = ((uint64_t)p.ldsb << 63) | ((uint64_t)p.ll << 62) | ((uint64_t)p.wpb << 40) | (uint64_t)p.lds;
+  if (okey == s->occ_key) occ = s->occ_val;
+  else {
+    rowpass_with(p, [&](auto k) { (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(k), (int)(64 * p.wpb), p.lds); });
+    s->occ_key = okey; s->occ_val = occ;
+  }
+  p.per_cu = std::max<uint32_t>(1, std::min<uint32_t>(8, (uint32_t)occ));
+  p.blocks = std::min<uint32_t>((s->R + p.wpb - 1) / p.wpb, s->ncu * p.per_cu);
+  return p;
+}
+
+// 2. broadcasts of round r-1 (with the external peers' Joins): the row pass, beside it side work 0 (the running set
+// and its fingerprint) and 1 (the latency sweep), then the Probes.  No host wait (but merge_ext_joins' two).
+static int round_broadcasts(kb_sim* s, Round& q) {
+  Dev& d = s->d;
+  const int32_t r = q.r;
+  const uint32_t R = s->R;
+  if (!s->inj_join.empty()) { const int rc = merge_ext_joins(s->st, s->bjoin, &s->nj, s->inj_join, 0, s->C); if (rc) return rc; }
+  PhaseB& pb = q.pb;
   pb.bfail = s->bfail; pb.nf = s->nf; pb.bjoin = s->bjoin; pb.nj = s->nj; pb.JW = (s->nj + 63) / 64;
   pb.nresp = s->nresp; pb.paysum = s->paysum; pb.nbase = s->nbase;
   if (pb.JW) {
     const size_t words = (size_t)R * pb.JW;
     if (words > s->mask_words) {
-      if (s->newmask_base) (void)hipFree(s->newmask_base);
-      if (s->respmask_base) (void)hipFree(s->respmask_base);
-      s->newmask_base = nullptr; s->respmask_base = nullptr;
-      HIPCHK(hipMalloc(&s->newmask_base, 8 * words)); HIPCHK(hipMalloc(&s->respmask_base, 8 * words));
-      s->mask_words = words;
+      const int rc = eng_grow_group(s, &s->mask_words, words, words, &s->newmask_base, &s->respmask_base);
+      if (rc) return rc;
     }
     s->newmask = bias(s->newmask_base, pb.JW, s->lo);
     s->respmask = bias(s->respmask_base, pb.JW, s->lo);
@@ -1364,121 +1356,103 @@ static int step_round(kb_sim* s) {
   pb.newmask = s->newmask; pb.respmask = s->respmask;
   pb.gid = s->bf_gid; pb.dep = s->bf_dep;
   // latency upkeep for Failed removals; socket_faithful never honours Failed, so nothing to do there
-  const bool lat_fail = d.lat && s->nf && d.failed_mode == KB_FAILED_SIM_SENDER;
-  pb.fnamed = lat_fail ? s->fnamed : nullptr;
-  if (lat_fail) klaunch(s, KI_LAT_MARK, k_lat_mark, dim3((s->nf + 255) / 256), dim3(256), 0, (const BCast*)s->bfail, s->nf, s->fnamed);
-  const bool have_b = s->nf + s->nj > 0;
+  q.lat_fail = d.lat && s->nf && d.failed_mode == KB_FAILED_SIM_SENDER;
+  pb.fnamed = q.lat_fail ? s->fnamed : nullptr;
+  if (q.lat_fail) klaunch(s, KI_LAT_MARK, k_lat_mark, dim3((s->nf + 255) / 256), dim3(256), 0, (const BCast*)s->bfail, s->nf, s->fnamed);
   const bool pb_hbm = (d.dbg & KB_DBG_PHASEB_HBM) != 0;
   if (s->nf > BFAIL_LDS_MAX || (pb_hbm && s->nf)) klaunch(s, KI_BFAIL_PREP, k_bfail_prep, dim3((s->nf + 255) / 256), dim3(256), 0, (const BCast*)s->bfail, s->nf, s->bf_gid, s->bf_dep, d.ctr + C_PATHS);
   else if (s->nf) klaunch(s, KI_BFAIL_PREP, k_bfail_prep_lds, dim3(1), dim3(1024), 0, (const BCast*)s->bfail, s->nf, s->bf_gid, s->bf_dep);
-  if (s->debug_waves && s->nf) {                     // KB_DEBUG_WAVES: broadcast list shape
-    std::vector<uint8_t> dep(s->nf);
-    HIPCHK(hipMemcpyAsync(dep.data(), s->bf_dep, s->nf, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    size_t nd = 0;
-    for (uint8_t x : dep) nd += x != 0;
-    fprintf(stderr, "[kb] round %d broadcasts: Failed %u (sender named earlier: %zu), Join %u\n", r, s->nf, nd, s->nj);
-  }
+  { const int rc = dbg_bcast_shape(s, r); if (rc) return rc; }
   {
-    // the row pass (broadcast phase + A3 candidates), persistent waves; broadcast lists staged in LDS
-    // once per workgroup when they fit.  Its events are taken by its own dispatch packet
-    // (hipExtLaunchKernel), so they time the kernel itself.
-    const uint32_t budget = RP_LDS_BYTES / 4;          // dynamic LDS words per workgroup
-    bool ll = s->nf <= PB_FMAX && s->nj <= PB_JMAX;   // both broadcast lists staged in LDS
-    uint32_t listw = ll ? 2 * s->nf + s->nj : 0;
-    if (listw > budget / 2 || pb_hbm) { ll = false; listw = 0; }
-    // the LDS variant stages each row's whole bitset for the Failed group's membership tests; without a
-    // Failed list (quiet rounds: A3 and a few Joins only) the row is read where A3 and the Joins touch it
-    // (372K peers, no broadcasts: 3.41 -> 0.54 ms, profiles/r04e_rowpass_variants.json).  (Rows too wide for
-    // more than 1-3 staged bitsets per workgroup still stage: the in-place variant with 8 waves per workgroup
-    // and the lists in LDS measured 17.4 -> 21.5 ms at 262K peers and 44.7 -> 41.8 ms at 372K in rounds with
-    // Failed lists, its random membership reads missing L2, profiles/r04s_nsweep.json)
-    const bool ldsb = s->W <= PB_LDS_W && budget - listw >= d.NWR && !pb_hbm && s->nf > 0;
-    const uint32_t wpb = ldsb ? std::min<uint32_t>(RP_WAVES, (budget - listw) / d.NWR) : RP_WAVES;
-    const size_t lds = 4ull * ((ldsb ? (size_t)wpb * d.NWR : 0) + listw);
-    int occ = 0;                                       // resident workgroups per CU (LDS, registers)
-    const void* rpk = ldsb ? (ll ? reinterpret_cast<const void*>(&k_rowpass<true, true>) : reinterpret_cast<const void*>(&k_rowpass<true, false>))
-                           : (ll ? reinterpret_cast<const void*>(&k_rowpass<false, true>) : reinterpret_cast<const void*>(&k_rowpass<false, false>));
-    const uint64_t okey = ((uint64_t)ldsb << 63) | ((uint64_t)ll << 62) | ((uint64_t)wpb << 40) | (uint64_t)lds;   // queried once per shape
-    if (okey == s->occ_key) occ = s->occ_val;
-    else {
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, rpk, (int)(64 * wpb), lds);
-      s->occ_key = okey; s->occ_val = occ;
-    }
-    const uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>(8, (uint32_t)occ));
-    const uint32_t blocks = std::min<uint32_t>((R + wpb - 1) / wpb, s->ncu * per_cu);
-    if (s->debug_waves && r == 2)
-      fprintf(stderr, "[kb] row pass: %u waves/workgroup, %zu B LDS, %u workgroups/CU (lds_per_cu %zu), %u workgroups\n", wpb,
-              lds, per_cu, (size_t)s->lds_per_cu, blocks);
-    const bool rp_prof = s->debug_waves && (d.dev & 2048);
-    if (rp_prof) HIPCHK(hipMemsetAsync(d.ctr + C_DBG_TNODE, 0, 4 * (C_DBG_MSGS - C_DBG_TNODE), st));
-    if (ldsb && !ll) s->host_paths |= PATH_ROWPASS_LDS_HBM_LISTS;   // coverage (test surface), with the device's bits
-    if (ldsb && ll) klaunch(s, KI_ROWPASS, k_rowpass<true, true>, dim3(blocks), dim3(64 * wpb), (uint32_t)lds, d, pb, s->ro, r);
-    else if (ldsb) klaunch(s, KI_ROWPASS, k_rowpass<true, false>, dim3(blocks), dim3(64 * wpb), (uint32_t)lds, d, pb, s->ro, r);
-    else if (ll) klaunch(s, KI_ROWPASS, k_rowpass<false, true>, dim3(blocks), dim3(64 * wpb), (uint32_t)lds, d, pb, s->ro, r);
-    else klaunch(s, KI_ROWPASS, k_rowpass<false, false>, dim3(blocks), dim3(64 * wpb), (uint32_t)lds, d, pb, s->ro, r);
-    if (rp_prof) {                                     // KB_DEV=2048: the row pass's phases, summed over its waves
-      uint32_t t[13];
-      HIPCHK(hipMemcpy(t, d.ctr + C_DBG_INS, 52, hipMemcpyDeviceToHost));
-      const double u = 100.0 / ((double)blocks * wpb);   // shares of the summed wall-clock ticks
-      double tot = 0;
-      for (int k = C_DBG_TNODE; k <= C_DBG_TEND; ++k) if (k != C_DBG_TMAX) tot += t[k - C_DBG_INS];
-      const double sc = tot > 0 ? (double)blocks * wpb / tot : 0;   // -> percent
-      fprintf(stderr, "[kb] round %d row pass time shares: stage %.1f %%, Failed %.1f %%, Join %.1f %%, A3 %.1f %%, write-back "
-              "%.1f %% (%u rows, %u waves)\n", r, t[C_DBG_TSTART - C_DBG_INS] * u * sc, t[C_DBG_TBASE - C_DBG_INS] * u * sc,
-              t[C_DBG_TINS - C_DBG_INS] * u * sc, t[C_DBG_TNODE - C_DBG_INS] * u * sc, t[C_DBG_TEND - C_DBG_INS] * u * sc, R,
-              blocks * wpb);
-    }
+    // the row pass; its events are taken by its own dispatch packet (hipExtLaunchKernel), so they time the kernel itself
+    const RowPlan p = rowpass_plan(s, pb_hbm);
+    { const int rc = dbg_rowpass_begin(s, r, p); if (rc) return rc; }
+    if (p.ldsb && !p.ll) s->host_paths |= PATH_ROWPASS_LDS_HBM_LISTS;   // coverage (test surface), with the device's bits
+    rowpass_with(p, [&](auto k) { klaunch(s, KI_ROWPASS, k, dim3(p.blocks), dim3(64 * p.wpb), (uint32_t)p.lds, d, pb, s->ro, r); });
+    { const int rc = dbg_rowpass_shares(s, r, p); if (rc) return rc; }
   }
   // beside the Join responses: the running set and its fingerprint (read by the tick's agreement count; the
   // set changed last with the churn), and the latency sweep (writes latency entries only; the tick's A2 and
   // the waves write them next)
   side_fork(s, 0);
-  klaunch_on(s, s->st2, KI_ALIVE_BITS, k_alive_bits, dim3((d.NWR + tb - 1) / tb), dim3(tb), 0, d);
+  klaunch_on(s, s->st2, KI_ALIVE_BITS, k_alive_bits, dim3((d.NWR + TB - 1) / TB), dim3(TB), 0, d);
   klaunch_on(s, s->st2, KI_TRUEFP_PART, k_truefp_part, dim3(TRUEFP_G), dim3(256), 0, d, d.tfpart);
   klaunch_on(s, s->st2, KI_TRUEFP_FIN, k_truefp_fin, dim3(1), dim3(64), 0, d, d.tfpart);
   side_done(s, 0);
-  if (lat_fail) {
+  if (q.lat_fail) {
     klaunch_on(s, s->st2, KI_LAT_SWEEP, k_lat_sweep, dim3((lat_stride(R) / 8 + 255) / 256, std::min<uint32_t>(s->nf, 16384)), dim3(256), 0, d,
             (const BCast*)s->bfail, (const uint32_t*)s->bf_gid, s->nf, s->fnamed);
     side_done(s, 1);
   }
   // the Probes queued since the last round travel with this round's broadcasts (after Failed and Join)
-  s->probes.swap(s->probe_q);
-  s->probe_q.clear();
-  const uint32_t np = (uint32_t)s->probes.size();
-  if (np) {
-    const size_t need = (size_t)np * R;
-    if (need > s->presp_cap) {
-      if (s->d_presp) (void)hipFree(s->d_presp);
-      s->d_presp = nullptr;
-      HIPCHK(hipMalloc(&s->d_presp, sizeof(uint2) * need));
-      s->presp_cap = need;
-    }
-    if (!s->d_presp_n) HIPCHK(hipMalloc(&s->d_presp_n, 4));
-    HIPCHK(hipMemsetAsync(s->d_presp_n, 0, 4, st));
-    klaunch(s, KI_PROBE, k_probe, dim3(gnode), dim3(tb), 0, d, np, r, s->d_presp, s->d_presp_n, (uint32_t)s->presp_cap);
+  { const int rc = round_take_probes(s, R, &q.np); if (rc) return rc; }
+  if (q.np) klaunch(s, KI_PROBE, k_probe, dim3(gnode(s)), dim3(TB), 0, d, q.np, r, s->d_presp, s->d_presp_n, (uint32_t)s->presp_cap);
+  return KB_OK;
+}
+
+// The round's Join responses into the wave-0 outbox: a wave per responder where its LDS slice fits (4 responders
+// per 64 KB workgroup); wider rows keep only the slice's head in LDS and select from the row itself (up to 4 waves
+// per workgroup, as the head fits: 3 at 1M-id rows); else (or forced) a workgroup with HBM scratch
+static int launch_join_responses(kb_sim* s, Round& q, uint32_t resp_nodes) {
+  Dev& d = s->d;
+  const int32_t r = q.r;
+  OutBuf& o0 = s->ob[0];
+  const uint32_t grid = std::min<uint32_t>(resp_nodes, 4096);   // (the workgroup path: 2 per CU when it serves only
+                                                               // the few responders the wave path lists)
+  const size_t words = resp_words(d.NWR, s->W / 256);
+  uint32_t* scratch = nullptr;
+  size_t lds = 4 * words;
+  const bool resp_hbm = s->W > RESP_LDS_W || (d.dbg & KB_DBG_RESP_HBM);
+  if (resp_hbm) {
+    { const int rc = eng_grow(s, &s->resp_scratch, &s->resp_scratch_words, words * grid); if (rc) return rc; }
+    scratch = s->resp_scratch;
+    lds = 0;
   }
+  const size_t wlds = 16ull * rwave_words(d.NWR, s->W / 256);
+  const size_t hlds = 4ull * rwave_head(s->W / 256);
+  const bool full_on = wlds <= 65536 && !(d.dbg & (KB_DBG_RESP_HBM | KB_DBG_RESP_WAVE_HBM));
+  const uint32_t hwaves = (uint32_t)std::min<size_t>(4, 65536 / hlds);
+  const bool head_on = !full_on && hwaves >= 1 && !(d.dbg & KB_DBG_RESP_HBM);
+  const bool wave_on = full_on || head_on;
+  { const int rc = dbg_resp_clear(s); if (rc) return rc; }
+  if (full_on) {                                   // timed by events on its own dispatch packet
+    klaunch(s, KI_RESP_WAVE, k_resp_wave<false>, dim3(std::min<uint32_t>((resp_nodes + 3) / 4, 4096)), dim3(256), (uint32_t)wlds, d,
+            q.pb, (const uint32_t*)s->resp_nodes, (const uint32_t*)(s->scan_tot + 4), o0, r, s->slow);
+  } else if (head_on) {
+    klaunch(s, KI_RESP_WAVE, k_resp_wave<true>, dim3(std::min<uint32_t>((resp_nodes + hwaves - 1) / hwaves, 4096)),
+            dim3(64 * hwaves), (uint32_t)(hwaves * hlds), d, q.pb, (const uint32_t*)s->resp_nodes,
+            (const uint32_t*)(s->scan_tot + 4), o0, r, s->slow);
+  }
+  // the workgroup path serves what the wave path left: its list (in the wave lists' slow buffer, free
+  // until the tick) when the wave path ran, else every responder
+  klaunch(s, KI_RESP_NODE, k_resp_node, dim3(wave_on ? std::min<uint32_t>(grid, 2 * s->ncu) : grid), dim3(256), (uint32_t)lds, d, q.pb,
+          (const uint32_t*)(wave_on ? s->slow : s->resp_nodes), (const uint32_t*)(wave_on ? d.ctr + C_RESTN : s->scan_tot + 4),
+          o0, r, scratch, wave_on);
+  return dbg_resp_report(s, r);
+}
+
+// Wave 0's outbox regions: the injected records' room, the scan (responses first, then the tick's messages) and
+// k_set_cap.  In a round with joiners or injected payloads the totals come back over the first pinned hand-off
+// (one host wait): the outbox and the export buffers grow to them, then the Join responses are written.
+static int round_wave0_regions(kb_sim* s, Round& q) {
+  Dev& d = s->d;
+  const int32_t r = q.r;
+  const uint32_t R = s->R;
+  OutBuf& o0 = s->ob[0];
   // records from external peers (kb_sim_inject): room for their KnownPeers ids in their wave-0 payload regions
-  const uint32_t ninj = (uint32_t)s->inj.size();
-  bool inj_pay = false;
-  if (ninj) {
-    if (ninj > s->d_inj_cap) {
-      if (s->d_inj) (void)hipFree(s->d_inj);
-      s->d_inj_cap = 2 * ninj;
-      HIPCHK(hipMalloc(&s->d_inj, sizeof(XRec) * s->d_inj_cap));
-    }
+  q.ninj = (uint32_t)s->inj.size();
+  if (q.ninj) {
+    if (q.ninj > s->d_inj_cap) { const int rc = eng_grow(s, &s->d_inj, &s->d_inj_cap, 2 * (size_t)q.ninj); if (rc) return rc; }
     if (s->inj_ids.size() > s->d_inj_ids_cap || !s->d_inj_ids) {
-      if (s->d_inj_ids) (void)hipFree(s->d_inj_ids);
-      s->d_inj_ids_cap = 2 * s->inj_ids.size() + 16;
-      HIPCHK(hipMalloc(&s->d_inj_ids, 4 * s->d_inj_ids_cap));
+      const int rc = eng_grow(s, &s->d_inj_ids, &s->d_inj_ids_cap, 2 * s->inj_ids.size() + 16);
+      if (rc) return rc;
     }
-    HIPCHK(hipMemcpyAsync(s->d_inj, s->inj.data(), sizeof(XRec) * ninj, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(s->d_inj, s->inj.data(), sizeof(XRec) * q.ninj, hipMemcpyHostToDevice, s->st));
     if (!s->inj_ids.empty()) {
-      HIPCHK(hipMemcpyAsync(s->d_inj_ids, s->inj_ids.data(), 4 * s->inj_ids.size(), hipMemcpyHostToDevice, st));
-      inj_pay = true;
+      HIPCHK(hipMemcpyAsync(s->d_inj_ids, s->inj_ids.data(), 4 * s->inj_ids.size(), hipMemcpyHostToDevice, s->st));
+      q.inj_pay = true;
     }
-    klaunch(s, KI_EVENTS, k_inject_prep, dim3(1), dim3(64), 0, d, (const XRec*)s->d_inj, ninj, s->paysum);
+    klaunch(s, KI_EVENTS, k_inject_prep, dim3(1), dim3(64), 0, d, (const XRec*)s->d_inj, q.ninj, s->paysum);
   }
   {  // wave-0 outbox regions: responses first, then the tick's messages
     ScanArgs a = scan_args(s, R, s->scan_tot);
@@ -1489,69 +1463,27 @@ static int step_round(kb_sim* s) {
     a.list = s->resp_nodes; a.list_base = s->lo;
     launch_scan(s, a);
   }
-  const bool need_tot = (have_b && s->nj) || inj_pay;
-  klaunch(s, KI_SET_CAP, k_set_cap, dim3(gnode), dim3(tb), 0, d, s->nresp, o0.cap, o0.cnt, s->scan_tot, s->d_pin, need_tot ? ++s->pin_seq : 0u);
-  if (need_tot) {
-    const uint32_t* tot = s->h_pin;                 // written by k_set_cap through the host mapping
-    { const int rc = wait_pin(s, s->pin_seq); if (rc) return rc; }
-    const uint32_t pay_tot = tot[1], msg_tot = tot[2], resp_nodes = tot[4];
-    if (msg_tot > o0.msg_cap || pay_tot > o0.pay_cap) {
-      const int rc = grow_wave0(s, msg_tot, pay_tot);
-      if (rc) return rc;
-    }
-    if (s->n_ext) { const int rc = size_exports(s, msg_tot, pay_tot); if (rc) return rc; }
-    if (resp_nodes) {
-      const uint32_t grid = std::min<uint32_t>(resp_nodes, 4096);   // (the workgroup path: 2 per CU when it serves only
-                                                                   // the few responders the wave path lists)
-      const size_t words = resp_words(d.NWR, s->W / 256);
-      uint32_t* scratch = nullptr;
-      size_t lds = 4 * words;
-      const bool resp_hbm = s->W > RESP_LDS_W || (d.dbg & KB_DBG_RESP_HBM);
-      if (resp_hbm) {
-        if (s->resp_scratch_words < words * grid) {
-          if (s->resp_scratch) (void)hipFree(s->resp_scratch);
-          HIPCHK(hipMalloc(&s->resp_scratch, 4 * words * grid));
-          s->resp_scratch_words = words * grid;
-        }
-        scratch = s->resp_scratch;
-        lds = 0;
-      }
-      // a wave per responder where its LDS slice fits (4 responders per 64 KB workgroup); wider rows keep
-      // only the slice's head in LDS and select from the row itself (up to 4 waves per workgroup, as the
-      // head fits: 3 at 1M-id rows); else (or forced) a workgroup with HBM scratch
-      const size_t wlds = 16ull * rwave_words(d.NWR, s->W / 256);
-      const size_t hlds = 4ull * rwave_head(s->W / 256);
-      const bool full_on = wlds <= 65536 && !(d.dbg & (KB_DBG_RESP_HBM | KB_DBG_RESP_WAVE_HBM));
-      const uint32_t hwaves = (uint32_t)std::min<size_t>(4, 65536 / hlds);
-      const bool head_on = !full_on && hwaves >= 1 && !(d.dbg & KB_DBG_RESP_HBM);
-      const bool wave_on = full_on || head_on;
-      if (s->debug_waves) HIPCHK(hipMemsetAsync(d.ctr + C_DBG_INS, 0, 52, st));
-      if (full_on) {                                   // timed by events on its own dispatch packet
-        klaunch(s, KI_RESP_WAVE, k_resp_wave<false>, dim3(std::min<uint32_t>((resp_nodes + 3) / 4, 4096)), dim3(256), (uint32_t)wlds, d,
-                pb, (const uint32_t*)s->resp_nodes, (const uint32_t*)(s->scan_tot + 4), o0, r, s->slow);
-      } else if (head_on) {
-        klaunch(s, KI_RESP_WAVE, k_resp_wave<true>, dim3(std::min<uint32_t>((resp_nodes + hwaves - 1) / hwaves, 4096)),
-                dim3(64 * hwaves), (uint32_t)(hwaves * hlds), d, pb, (const uint32_t*)s->resp_nodes,
-                (const uint32_t*)(s->scan_tot + 4), o0, r, s->slow);
-      }
-      // the workgroup path serves what the wave path left: its list (in the wave lists' slow buffer, free
-      // until the tick) when the wave path ran, else every responder
-      klaunch(s, KI_RESP_NODE, k_resp_node, dim3(wave_on ? std::min<uint32_t>(grid, 2 * s->ncu) : grid), dim3(256), (uint32_t)lds, d, pb,
-              (const uint32_t*)(wave_on ? s->slow : s->resp_nodes), (const uint32_t*)(wave_on ? d.ctr + C_RESTN : s->scan_tot + 4),
-              o0, r, scratch, wave_on);
-      if (s->debug_waves && (d.dev & 512)) {
-        uint32_t dbg[13];
-        HIPCHK(hipMemcpyAsync(dbg, d.ctr + C_DBG_INS, 52, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        fprintf(stderr, "[kb] round %d k_resp_wave: responders %u, responses %u: row staging %.1f us, joiners %.1f, prefix %.1f, "
-                "fills %.1f (sums over waves)\n", r, dbg[10], dbg[12], dbg[11] * 0.01, dbg[8] * 0.01, dbg[6] * 0.01, dbg[9] * 0.01);
-      }
-    }
-  }
-  // 3. tick
-  if (lat_fail) side_join(s, 1);
-  klaunch(s, KI_TICK_SCAN, k_tick_scan, dim3(gnode), dim3(tb), 0, d, s->bs, r, s->slow);                       // A1; list the A2 nodes
-  klaunch(s, KI_TICK_PRE, k_tick_pre, dim3(std::min<uint32_t>(gwave, 1024)), dim3(256), 0, d, o0, s->bs, r, s->slow);   // A2 per listed node
+  const bool need_tot = s->nj > 0 || q.inj_pay;      // only Joins and injected payloads can outgrow the outbox
+  klaunch(s, KI_SET_CAP, k_set_cap, dim3(gnode(s)), dim3(TB), 0, d, s->nresp, o0.cap, o0.cnt, s->scan_tot, s->d_pin, need_tot ? ++s->pin_seq : 0u);
+  if (!need_tot) return KB_OK;
+  const uint32_t* tot = s->h_pin;                    // written by k_set_cap through the host mapping
+  { const int rc = wait_pin(s, s->pin_seq); if (rc) return rc; }
+  const uint32_t pay_tot = tot[1], msg_tot = tot[2], resp_nodes = tot[4];
+  if (msg_tot > o0.msg_cap || pay_tot > o0.pay_cap) { const int rc = grow_wave0(s, msg_tot, pay_tot); if (rc) return rc; }
+  if (s->n_ext) { const int rc = round_size_exports(s, msg_tot, pay_tot); if (rc) return rc; }
+  return resp_nodes ? launch_join_responses(s, q, resp_nodes) : KB_OK;
+}
+
+// 3. tick: A1, A2, the fold and the row fingerprints, with the exact A3 order (side work 2) beside the fold; side
+// work 0, 1 and 2 join here.  Then the injected records' emissions and the round's broadcast lists.  No host wait.
+static int round_tick(kb_sim* s, Round& q) {
+  Dev& d = s->d;
+  const int32_t r = q.r;
+  const uint32_t R = s->R, gn = gnode(s);
+  OutBuf& o0 = s->ob[0];
+  if (q.lat_fail) side_join(s, 1);
+  klaunch(s, KI_TICK_SCAN, k_tick_scan, dim3(gn), dim3(TB), 0, d, s->bs, r, s->slow);                       // A1; list the A2 nodes
+  klaunch(s, KI_TICK_PRE, k_tick_pre, dim3(std::min<uint32_t>((R + 3) / 4, 1024)), dim3(256), 0, d, o0, s->bs, r, s->slow);   // A2 per listed node
   // exact A3 order beside the fold: it reads what A2 left (member bits, stamps, instants, bounds) and writes only
   // the five keys and the bounds, which nothing else reads before k_tick_post; the fold and the row fingerprints
   // write checkpoints and fingerprints only
@@ -1565,12 +1497,12 @@ static int step_round(kb_sim* s) {
   }
   // every checkpoint the round's membership changes (broadcasts, A2) made stale is refolded
   if (d.uniform) klaunch(s, KI_FOLD, k_fold, dim3(((R + 63) / 64 + 3) / 4 * s->S), dim3(256), 0, d, FoldArgs{s->S});
-  if (d.uniform) klaunch(s, KI_FP_ROWS, k_fp_rows, dim3((FP_LANES * R + tb - 1) / tb), dim3(tb), 0, d);
+  if (d.uniform) klaunch(s, KI_FP_ROWS, k_fp_rows, dim3((FP_LANES * R + TB - 1) / TB), dim3(TB), 0, d);
   side_join(s, 0);
   if (d.tst) side_join(s, 2);
-  klaunch(s, KI_TICK_POST, k_tick_post, dim3(gnode), dim3(tb), 0, d, s->ro, o0, r);
-  if (ninj) {                                          // the external peers' wave-0 emissions, after the tick's
-    klaunch(s, KI_EVENTS, k_inject, dim3(1), dim3(64), 0, d, o0, (const XRec*)s->d_inj, ninj, (const uint32_t*)s->d_inj_ids);
+  klaunch(s, KI_TICK_POST, k_tick_post, dim3(gn), dim3(TB), 0, d, s->ro, o0, r);
+  if (q.ninj) {                                        // the external peers' wave-0 emissions, after the tick's
+    klaunch(s, KI_EVENTS, k_inject, dim3(1), dim3(64), 0, d, o0, (const XRec*)s->d_inj, q.ninj, (const uint32_t*)s->d_inj_ids);
     s->inj.clear(); s->inj_ids.clear();
   }
   {
@@ -1580,91 +1512,84 @@ static int step_round(kb_sim* s) {
     a.in[1] = L(s, s->bs.nfail); a.out[1] = L(s, s->fail_off);
     launch_scan(s, a);
   }
-  klaunch(s, KI_BCAST_WRITE, k_bcast_write, dim3(gnode), dim3(tb), 0, d, s->bs, (const uint32_t*)s->join_off,
+  klaunch(s, KI_BCAST_WRITE, k_bcast_write, dim3(gn), dim3(TB), 0, d, s->bs, (const uint32_t*)s->join_off,
           (const uint32_t*)s->fail_off, s->xf ? s->bjoin_loc : s->bjoin, s->xf ? s->bfail_loc : s->bfail);
-  // 4. receive window: unicast waves.  Unsharded, the window has no host decision inside it, so with
-  // KB_WAVE_GRAPH=1 its ≈ 80 launches are one HIP graph, captured once per buffer generation and
-  // replayed each round: that removes host launch gaps in multi-round steps, but the benched one-round
-  // steps are GPU-bound and measured no faster, so it is off by default.
-  if (!s->xf && !s->debug_waves && s->graph_on) {
-    if (!s->wave_exec || s->wave_gen != s->buf_gen) {
-      if (s->wave_exec) { (void)hipGraphExecDestroy(s->wave_exec); s->wave_exec = nullptr; }
-      if (s->wave_graph) { (void)hipGraphDestroy(s->wave_graph); s->wave_graph = nullptr; }
-      HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      s->capturing = true;                           // captured launches carry no profile events
-      const int rc = launch_waves(s, -1);
-      s->capturing = false;
-      hipGraph_t g = nullptr;
-      const hipError_t e = hipStreamEndCapture(st, &g);
-      if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-      HIPCHK(e);
-      s->wave_graph = g;
-      HIPCHK(hipGraphInstantiate(&s->wave_exec, g, nullptr, nullptr, 0));
-      s->wave_gen = s->buf_gen;
-    }
-    HIPCHK(hipGraphLaunch(s->wave_exec, st));
-  } else {
-    const int rc = launch_waves(s, r);
-    if (rc) return rc;
+  return KB_OK;
+}
+
+// 4. receive window: unicast waves.  Unsharded, the window has no host decision inside it, so with
+// KB_WAVE_GRAPH=1 its ≈ 80 launches are one HIP graph, captured once per buffer generation and
+// replayed each round: that removes host launch gaps in multi-round steps, but the benched one-round
+// steps are GPU-bound and measured no faster, so it is off by default.
+static int round_window(kb_sim* s, Round& q) {
+  hipStream_t st = s->st;
+  if (s->xf || s->debug_waves || !s->graph_on) return launch_waves(s, q.r);
+  if (!s->wave_exec || s->wave_gen != s->buf_gen) {
+    if (s->wave_exec) { (void)hipGraphExecDestroy(s->wave_exec); s->wave_exec = nullptr; }
+    if (s->wave_graph) { (void)hipGraphDestroy(s->wave_graph); s->wave_graph = nullptr; }
+    HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    s->capturing = true;                           // captured launches carry no profile events
+    const int rc = launch_waves(s, -1);
+    s->capturing = false;
+    hipGraph_t g = nullptr;
+    const hipError_t e = hipStreamEndCapture(st, &g);
+    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+    HIPCHK(e);
+    s->wave_graph = g;
+    HIPCHK(hipGraphInstantiate(&s->wave_exec, g, nullptr, nullptr, 0));
+    s->wave_gen = s->buf_gen;
   }
+  HIPCHK(hipGraphLaunch(s->wave_exec, st));
+  return KB_OK;
+}
+
+// The round's end: the agreement count, k_round_end, and the one host wait every round has: sharded, the all-gather
+// of every shard's broadcast lists and error flag (gather_broadcasts); else the second pinned hand-off, k_round_end's
+// counts and error flag in the host-mapped buffer (the stream then drains by itself).  The earlier rounds' profile
+// events are read while this round runs.  Then the two drains (round_drain_*: blocking copies).
+static int round_finish(kb_sim* s, Round& q) {
+  Dev& d = s->d;
+  const int32_t r = q.r;
+  hipStream_t st = s->st;
   if (s->xf && !s->xf->allreduce_sum_u32(d.ctr + C_AGREE, 1, st)) { seterr(s->xf->error()); return KB_IO_ERROR; }
   klaunch(s, KI_ROUND_END, k_round_end, dim3(1), dim3(1), 0, d, r, (const uint32_t*)s->scan_tot, s->d_pin,
           s->xf ? 0u : ++s->pin_seq, s->rr);
-  (void)hipEventRecord(er[1], st);
-  s->krec.push_back(kb_sim::KRec{(int16_t)NKI, (int16_t)-1, er[0], er[1]});
-  // the earlier rounds' kernel events are complete: read them while this round runs
-  prof_resolve(s, krec0);
+  (void)hipEventRecord(q.er[1], st);
+  s->krec.push_back(kb_sim::KRec{(int16_t)NKI, (int16_t)-1, q.er[0], q.er[1]});
+  prof_resolve(s, q.krec0);
   uint32_t err = 0;
   if (s->xf) {
-    // every shard's broadcast lists and error flag in one all-gather, one host wait
     const int rc = gather_broadcasts(s, &err);
     if (rc) return rc;
   } else {
-    // k_round_end wrote the next round's broadcast counts and the error flag straight into the
-    // host-mapped pinned buffer; the host polls for them (the stream then drains by itself)
     const int rc = wait_pin(s, s->pin_seq);
     if (rc) return rc;
     s->nj = s->h_pin[0]; s->nf = s->h_pin[1]; err = s->h_pin[2];
   }
   s->bj_total += s->nj; s->bf_total += s->nf;
-  if (s->n_ext) {                                      // the round's records to external peers, to the host queue
-    uint32_t c[2];
-    HIPCHK(hipMemcpy(c, d.ctr + C_XREC, 8, hipMemcpyDeviceToHost));
-    const uint32_t nrec = std::min(c[0], d.xrec_cap), nid = std::min(c[1], d.xids_cap);
-    std::vector<XRec> v(nrec);
-    const size_t base = s->xq_ids.size();
-    s->xq_ids.resize(base + nid);
-    if (nrec) HIPCHK(hipMemcpy(v.data(), d.xrec, sizeof(XRec) * nrec, hipMemcpyDeviceToHost));
-    if (nid) HIPCHK(hipMemcpy(s->xq_ids.data() + base, d.xids, 4ull * nid, hipMemcpyDeviceToHost));
-    std::sort(v.begin(), v.end(), [](const XRec& a, const XRec& b) {
-      return a.wave != b.wave ? a.wave < b.wave : a.sender != b.sender ? a.sender < b.sender : a.seq < b.seq; });
-    for (const XRec& x : v) {
-      kb_unicast u;
-      memcpy(&u, &x, sizeof u);
-      u.pay_off = (uint32_t)(base + x.pay_off);
-      s->xq.push_back(u);
-    }
-    const uint32_t z[2] = {0, 0};
-    HIPCHK(hipMemcpy(d.ctr + C_XREC, z, 8, hipMemcpyHostToDevice));
-  }
-  if (np) {                                          // the round's ProbeResponses, (responder, probe) order
-    uint32_t k = 0;
-    HIPCHK(hipMemcpy(&k, s->d_presp_n, 4, hipMemcpyDeviceToHost));
-    k = std::min<uint32_t>(k, (uint32_t)s->presp_cap);
-    std::vector<uint2> v(k);
-    if (k) HIPCHK(hipMemcpy(v.data(), s->d_presp, sizeof(uint2) * k, hipMemcpyDeviceToHost));
-    std::sort(v.begin(), v.end(), [](const uint2& a, const uint2& b) { return a.x != b.x ? a.x < b.x : a.y < b.y; });
-    for (const uint2& q : v) {
-      kb_probe_response o;
-      memset(&o, 0, sizeof o);
-      o.responder = q.x; o.probe = q.y; o.round = r; o.prober = s->probes[q.y];
-      o.identity_len = s->h_idlen[q.x];
-      memcpy(o.identity, &s->h_ident[(size_t)q.x * MAXID], o.identity_len);
-      s->presp.push_back(o);
-    }
-  }
+  { const int rc = round_drain_exports(s); if (rc) return rc; }
+  { const int rc = round_drain_probes(s, q.np, r); if (rc) return rc; }
   s->round = r + 1;
   return err_status(err);                            // shards: the flag of any rank
+}
+
+static int step_round(kb_sim* s) {
+  Round q;
+  q.r = s->round;
+  q.krec0 = s->krec.size();
+  s->cur_wave = -1;
+  for (int k = 0; k < 2; ++k) {
+    if (!s->ev_free.empty()) { q.er[k] = s->ev_free.back(); s->ev_free.pop_back(); }
+    else (void)hipEventCreate(&q.er[k]);
+  }
+  (void)hipEventRecord(q.er[0], s->st);
+  int rc = round_lifecycle(s, q);
+  if (!rc) rc = round_broadcasts(s, q);
+  if (!rc) rc = round_wave0_regions(s, q);
+  if (!rc) rc = round_tick(s, q);
+  if (!rc) rc = round_window(s, q);
+  if (!rc) rc = round_finish(s, q);
+  return rc;
 }
 
 // every shard of a group steps in its own thread; a failing shard aborts the others' rendezvous
@@ -1731,7 +1656,7 @@ static int mark_all_dirty(kb_sim* s) {
 }
 static void window_stale(kb_sim* s) { s->buf_gen++; }   // a captured receive window holds the old Dev and buffers
 static int export_alloc(kb_sim* s) {
-  s->d.xrec_cap = XREC_MIN; s->d.xids_cap = XIDS_MIN;   // grown per round (size_exports)
+  s->d.xrec_cap = XREC_MIN; s->d.xids_cap = XIDS_MIN;   // grown per round (round_size_exports)
   HIPCHK(talloc(s, &s->d.xrec, s->d.xrec_cap)); HIPCHK(talloc(s, &s->d.xids, s->d.xids_cap));
   window_stale(s);
   return KB_OK;

@@ -119,18 +119,12 @@ template <class T> static hipError_t sp_ralloc(SpSim* S, T** p, size_t per_row) 
   return e;
 }
 template <class T> static T* SL(const SpSim* S, T* p) { return p + S->lo; }
-// a dynamic buffer of at least `need` elements (contents are not kept)
+template <class T> static hipError_t eng_alloc(SpSim* S, T** p, size_t n) { return sp_alloc(S, p, n); }   // kb_roundframe.h's hooks
+static const char* eng_alloc_what(SpSim*) { return "sparse engine: device allocation failed: "; }
+// a dynamic buffer of at least `need` elements (contents are not kept), grown with a quarter's slack
 template <class T> static int sp_grow(SpSim* S, T** p, size_t* cap, size_t need) {
   if (need <= *cap && *p) return KB_OK;
-  for (auto& q : S->allocs) if (q == (void*)*p) q = nullptr;
-  S->allocs.erase(std::remove(S->allocs.begin(), S->allocs.end(), nullptr), S->allocs.end());
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  const size_t c = std::max<size_t>(need + need / 4, 1024);
-  const hipError_t e = sp_alloc(S, p, c);
-  if (e != hipSuccess) { *cap = 0; seterr(std::string("sparse engine: device allocation failed: ") + hipGetErrorString(e)); return KB_CAPACITY; }
-  *cap = c;
-  return KB_OK;
+  return eng_grow(S, p, cap, std::max<size_t>(need + need / 4, 1024));
 }
 static void sp_prof(SpSim* S, int kid, hipEvent_t* a, hipEvent_t* b) {
   *a = *b = nullptr;
@@ -198,8 +192,6 @@ static void sp_destroy(SpSim* S) {
   (void)hipSetDevice(S->device);
   if (S->st) (void)hipStreamSynchronize(S->st);
   for (void* p : S->allocs) (void)hipFree(p);
-  if (S->d_events) (void)hipFree(S->d_events);
-  if (S->d_presp) (void)hipFree(S->d_presp);
   for (auto& q : S->recs) { (void)hipEventDestroy(q.a); (void)hipEventDestroy(q.b); }
   for (hipEvent_t e : S->ev_free) (void)hipEventDestroy(e);
   if (S->st) (void)hipStreamDestroy(S->st);
@@ -376,12 +368,7 @@ static int sp_apply_events(SpSim* S, int32_t r) {
   const uint32_t C = S->C;
   if (S->events.empty()) return KB_OK;
   if (S->xf) for (Event& ev : S->events) if (ev.kind == EV_RESTART) ev.kind = EV_START_MOVED;   // the row moves on the host
-  if (S->events.size() > S->events_cap) {
-    if (S->d_events) (void)hipFree(S->d_events);
-    S->events_cap = S->events.size() * 2;
-    HIPCHK(hipMalloc(&S->d_events, sizeof(Event) * S->events_cap));
-  }
-  HIPCHK(hipMemcpyAsync(S->d_events, S->events.data(), sizeof(Event) * S->events.size(), hipMemcpyHostToDevice, S->st));
+  { const int rc = round_upload_events(S); if (rc) return rc; }
   size_t k0 = 0;
   for (size_t k = 0; k < S->events.size(); ++k) {
     const Event& ev = S->events[k];
@@ -536,20 +523,8 @@ static int sp_step_round(SpSim* S) {
     const int rc = merge_ext_joins(S->st, S->bjoin, &S->nj, S->inj_join, S->cfg.partition_groups, C);
     if (rc) return rc;
   }
-  S->probes.swap(S->probe_q);
-  S->probe_q.clear();
-  const uint32_t np = (uint32_t)S->probes.size();
-  if (np) {
-    const size_t need = (size_t)np * R;
-    if (need > S->presp_cap) {
-      if (S->d_presp) (void)hipFree(S->d_presp);
-      S->d_presp = nullptr;
-      HIPCHK(hipMalloc(&S->d_presp, sizeof(uint2) * need));
-      S->presp_cap = need;
-    }
-    if (!S->d_presp_n) HIPCHK(sp_alloc(S, &S->d_presp_n, 1));
-    HIPCHK(hipMemsetAsync(S->d_presp_n, 0, 4, st));
-  }
+  uint32_t np = 0;
+  { const int rc = round_take_probes(S, R, &np); if (rc) return rc; }
   SpBc bc;
   memset(&bc, 0, sizeof bc);
   bc.bfail = S->bfail; bc.nf = S->nf; bc.bjoin = S->bjoin; bc.nj = S->nj; bc.JW = (S->nj + 31) / 32;
@@ -582,8 +557,8 @@ static int sp_step_round(SpSim* S) {
   for (const XRec& q : S->inj) if (q.sender >= S->lo && q.sender < S->hi) inj.push_back(q);
   const uint32_t ninj = (uint32_t)inj.size();
   if (ninj) {
-    { size_t c = S->d_inj_cap; const int rc = sp_grow(S, &S->d_inj, &c, ninj); if (rc) return rc; S->d_inj_cap = c; }
-    { size_t c = S->d_inj_ids_cap; const int rc = sp_grow(S, &S->d_inj_ids, &c, S->inj_ids.size() + 1); if (rc) return rc; S->d_inj_ids_cap = c; }
+    { const int rc = sp_grow(S, &S->d_inj, &S->d_inj_cap, ninj); if (rc) return rc; }
+    { const int rc = sp_grow(S, &S->d_inj_ids, &S->d_inj_ids_cap, S->inj_ids.size() + 1); if (rc) return rc; }
     HIPCHK(hipMemcpyAsync(S->d_inj, inj.data(), sizeof(XRec) * ninj, hipMemcpyHostToDevice, st));
     if (!S->inj_ids.empty()) HIPCHK(hipMemcpyAsync(S->d_inj_ids, S->inj_ids.data(), 4 * S->inj_ids.size(), hipMemcpyHostToDevice, st));
     sp_launch(S, SPK_EVENTS, k_sp_inject_prep, 1, 1, d, (const XRec*)S->d_inj, ninj, S->ebound, S->jr_pay);
@@ -598,12 +573,7 @@ static int sp_step_round(SpSim* S) {
   HIPCHK(sp_sync(S));
   { const int rc = sp_grow(S, &S->stage, &S->stage_cap, tot[0]); if (rc) return rc; }
   { const int rc = sp_grow(S, &S->pool[0], &S->pool_cap[0], tot[1]); if (rc) return rc; }
-  if (S->n_ext) {                                    // exports of the round: wave 0's totals + the later waves' allowance
-    const uint64_t nr = (uint64_t)tot[0] + (1u << 16), ni = (uint64_t)tot[1] + (1u << 22);   // (kb_sim.hip size_exports)
-    if (nr > 0xFFFFFFFFull || ni > 0xFFFFFFFFull) { seterr("export buffer beyond 2^32 entries"); return KB_CAPACITY; }
-    if (nr > d.xrec_cap) { size_t c = d.xrec_cap; const int rc = sp_grow(S, &d.xrec, &c, nr); if (rc) return rc; d.xrec_cap = (uint32_t)std::min<size_t>(c, 0xFFFFFFFFu); }
-    if (ni > d.xids_cap) { size_t c = d.xids_cap; const int rc = sp_grow(S, &d.xids, &c, ni); if (rc) return rc; d.xids_cap = (uint32_t)std::min<size_t>(c, 0xFFFFFFFFu); }
-  }
+  if (S->n_ext) { const int rc = round_size_exports(S, tot[0], tot[1]); if (rc) return rc; }   // wave 0's totals + the later waves' allowance
   SpOut o0;
   o0.stage = S->stage; o0.eoff = S->eoff; o0.ecap = S->ebound; o0.pay = S->pool[0]; o0.poff = S->poff; o0.pcap = S->jr_pay;
   o0.en = S->en;
@@ -702,42 +672,8 @@ static int sp_step_round(SpSim* S) {
   if (S->prof_level > 0) sp_prof_resolve(S);
   S->nj = nj_next; S->nf = nf_next;
   S->bj_total += nj_next; S->bf_total += nf_next;
-  if (S->n_ext) {                                    // the round's records to external peers, to the host queue
-    uint32_t c[2];
-    HIPCHK(hipMemcpy(c, d.ctr + C_XREC, 8, hipMemcpyDeviceToHost));
-    const uint32_t nrec = std::min(c[0], d.xrec_cap), nid = std::min(c[1], d.xids_cap);
-    std::vector<XRec> v(nrec);
-    const size_t base = S->xq_ids.size();
-    S->xq_ids.resize(base + nid);
-    if (nrec) HIPCHK(hipMemcpy(v.data(), d.xrec, sizeof(XRec) * nrec, hipMemcpyDeviceToHost));
-    if (nid) HIPCHK(hipMemcpy(S->xq_ids.data() + base, d.xids, 4ull * nid, hipMemcpyDeviceToHost));
-    std::sort(v.begin(), v.end(), [](const XRec& a, const XRec& b) {
-      return a.wave != b.wave ? a.wave < b.wave : a.sender != b.sender ? a.sender < b.sender : a.seq < b.seq; });
-    for (const XRec& q : v) {
-      kb_unicast u;
-      memcpy(&u, &q, sizeof u);
-      u.pay_off = (uint32_t)(base + q.pay_off);
-      S->xq.push_back(u);
-    }
-    const uint32_t z[2] = {0, 0};
-    HIPCHK(hipMemcpy(d.ctr + C_XREC, z, 8, hipMemcpyHostToDevice));
-  }
-  if (np) {                                          // the round's ProbeResponses, (responder, probe) order
-    uint32_t k = 0;
-    HIPCHK(hipMemcpy(&k, S->d_presp_n, 4, hipMemcpyDeviceToHost));
-    k = (uint32_t)std::min<size_t>(k, S->presp_cap);
-    std::vector<uint2> v(k);
-    if (k) HIPCHK(hipMemcpy(v.data(), S->d_presp, sizeof(uint2) * k, hipMemcpyDeviceToHost));
-    std::sort(v.begin(), v.end(), [](const uint2& a, const uint2& b) { return a.x != b.x ? a.x < b.x : a.y < b.y; });
-    for (const uint2& q : v) {
-      kb_probe_response o;
-      memset(&o, 0, sizeof o);
-      o.responder = q.x; o.probe = q.y; o.round = r; o.prober = S->probes[q.y];
-      o.identity_len = S->h_idlen[q.x];
-      memcpy(o.identity, &S->h_ident[(size_t)q.x * MAXID], o.identity_len);
-      S->presp.push_back(o);
-    }
-  }
+  { const int rc = round_drain_exports(S); if (rc) return rc; }
+  { const int rc = round_drain_probes(S, np, r); if (rc) return rc; }
   S->round = r + 1;
   return sp_err_status(err);
 }
@@ -783,7 +719,7 @@ static int mark_all_dirty(SpSim* S) {
   return KB_OK;
 }
 static int export_alloc(SpSim* S) {
-  S->d.xrec_cap = 1u << 16; S->d.xids_cap = 1u << 22;
+  S->d.xrec_cap = XREC_MIN; S->d.xids_cap = XIDS_MIN;   // grown per round (round_size_exports)
   HIPCHK(sp_alloc(S, &S->d.xrec, S->d.xrec_cap)); HIPCHK(sp_alloc(S, &S->d.xids, S->d.xids_cap));
   return KB_OK;
 }
