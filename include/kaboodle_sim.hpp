@@ -17,6 +17,7 @@
 #include "kaboodle_latency.h"
 #include "kaboodle_age.h"
 #include "kaboodle_delta.h"
+#include "kaboodle_islands.h"
 
 namespace kb {
 
@@ -154,6 +155,18 @@ class Mesh {
     check(kb_sim_delta_census(h_, &r.summary, p(r.gained_by), p(r.lost_by), r.gained_by.size(), p(r.gained), p(r.lost),
                               p(r.lost_live), r.gained.size(), advance ? KB_DELTA_ADVANCE : 0u),
           "kb_sim_delta_census");
+    return r;
+  }
+
+  // the island census (kaboodle_islands.h; HIP library only, dense handles): the connected components of the
+  // "i holds j" graph over the running peers.  Per id: the lowest id of its island (KB_CENSUS_NONE where it does not
+  // run) and the island's size.  arrays = false asks for the summary alone.
+  struct Islands { kb_islands summary; std::vector<uint32_t> label, size; };
+  Islands islands(bool arrays = true) const {
+    Islands r;
+    if (arrays) { r.label.resize(capacity_); r.size.resize(capacity_); }
+    check(kb_sim_islands(h_, &r.summary, arrays ? r.label.data() : nullptr, arrays ? r.size.data() : nullptr, r.label.size()),
+          "kb_sim_islands");
     return r;
   }
 

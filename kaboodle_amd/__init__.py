@@ -161,6 +161,16 @@ class Mesh(Sim):
         """Free the baseline; delta_census raises KbError until the next delta_mark."""
         super().delta_release()
 
+    def islands(self, arrays: bool = True):
+        """Which peers can still reach each other (include/kaboodle_islands.h): the connected
+        components of the "i holds j" graph over the running peers, labelled on the GPU with their lowest id.  Two
+        islands never learn of each other again without a new joiner, a restart, ping_addrs or an external peer.
+        Returns an `islands.Islands`: the summary (islands, singletons, those that broadcast Join again, the largest
+        and second largest, the unreachable ordered pairs, the eight largest as (label, size)) and per id the label
+        and size of its island.  Dense rows, unsharded or in-process shards; sparse rows and rank shards raise
+        KbError."""
+        return super().islands(arrays)
+
 
 def latency_census_of(lat, member, running, arrays: bool = True, device: int = 0):
     """The latency census's GPU kernel over host arrays (kb_latency_census_of, a test surface): `lat` peer-major
@@ -181,6 +191,13 @@ def delta_of(bits_base, run_base, bits_now, run_now, external, row_lo: int = 0, 
     mark and now, the two running sets and the external ids per id; a `delta.DeltaCensus`."""
     from ._ffi import delta_of as _of
     return _of(lib(), bits_base, run_base, bits_now, run_now, external, row_lo, rpw, arrays, device)
+
+
+def islands_of(bits, running, arrays: bool = True, device: int = 0):
+    """The island census's GPU kernels over host arrays (kb_islands_of, a test surface): member bits
+    [capacity][W/32] of every row and the running set per id; an `islands.Islands`."""
+    from ._ffi import islands_of as _of
+    return _of(lib(), bits, running, arrays, device)
 
 
 def discover_mesh_member(mesh: "Mesh", prober=("192.0.2.1", 40000), max_rounds: int = 64):

@@ -216,6 +216,24 @@ class KbDelta(C.Structure):
 _DELTA_OUT = [C.POINTER(KbDelta), *[C.POINTER(C.c_uint32)] * 2, C.c_size_t, *[C.POINTER(C.c_uint32)] * 3, C.c_size_t]
 
 
+KB_ISLANDS_TOP = 8               # islands listed in kb_islands.top
+
+
+class KbIslands(C.Structure):
+    """kb_islands (include/kaboodle_islands.h)."""
+    _fields_ = [("round", C.c_int32), ("observers", C.c_uint32), ("islands", C.c_uint32), ("singletons", C.c_uint32),
+                ("rebroadcasting", C.c_uint32), ("largest", C.c_uint32), ("largest_label", C.c_uint32),
+                ("second", C.c_uint32), ("unreachable_pairs", C.c_uint64), ("top", C.c_uint32 * 2 * KB_ISLANDS_TOP),
+                ("sweeps", C.c_uint32), ("pad", C.c_uint32), ("reserved", C.c_uint64 * 4)]
+
+    def as_dict(self) -> dict:
+        top = [[int(e[0]), int(e[1])] for e in self.top]
+        return {n: top if n == "top" else int(getattr(self, n)) for n, _ in self._fields_ if n not in ("reserved", "pad")}
+
+
+_ISLANDS_OUT = [C.POINTER(KbIslands), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t]
+
+
 KB_SNAPSHOT_VERSION = 1
 
 
@@ -422,6 +440,11 @@ _OPTIONAL = {
     "delta_of": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32),
                            C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32,
                            *_DELTA_OUT]),
+    # the island census (include/kaboodle_islands.h; HIP library only, the oracle answers through
+    # islands.islands_of_sim)
+    "sim_islands": (C.c_int, [C.c_void_p, *_ISLANDS_OUT]),
+    "sim_islands_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "islands_of": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_size_t, *_ISLANDS_OUT]),
     # snapshot and restore (include/kaboodle_snapshot.h; HIP library only)
     "snapshot_info_of": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(KbSnapshotInfo)]),
     "sim_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
@@ -553,6 +576,24 @@ def delta_of(lib: SimLib, bits_base, run_base, bits_now, run_now, external, row_
     lib.call("delta_of", device, p32(b0), p8(rb), p32(b1), p8(rn), p8(ex), cap, row_lo, b0.shape[0], rpw,
              C.byref(out), *args)
     return DeltaCensus(out.as_dict(), *outs)
+
+
+def islands_of(lib: SimLib, bits, running, arrays: bool = True, device: int = 0):
+    """kb_islands_of: the island census's kernels over host arrays (a test surface, include/kaboodle_islands.h).  bits:
+    uint32 [capacity, W/32] member bits of every row (W = capacity rounded up to 8192); running: a flag per id
+    ([capacity]).  An `Islands` with round -1.  KbError(KB_NO_DEVICE) without a GPU."""
+    import numpy as np
+    from .islands import Islands
+    run = np.ascontiguousarray(np.asarray(running) != 0, dtype=np.uint8)
+    cap = len(run)
+    b = np.ascontiguousarray(bits, dtype=np.uint32)
+    if b.ndim != 2 or b.shape != (cap, (cap + 8191) // 8192 * 8192 // 32):
+        raise ValueError("islands_of: array shapes do not match the capacity")
+    out = KbIslands()
+    outs, args = _out_arrays(arrays, (["u4"] * 2, cap))
+    lib.call("islands_of", device, b.ctypes.data_as(C.POINTER(C.c_uint32)), run.ctypes.data_as(C.POINTER(C.c_uint8)),
+             cap, C.byref(out), *args)
+    return Islands(out.as_dict(), *outs)
 
 
 class Sim:
@@ -892,6 +933,26 @@ class Sim:
         """Device time of the last delta_census() in ms (kb_sim_delta_device_ms; HIP library only); 0.0 before the
         first answer."""
         return self._device_ms("delta")
+
+    def islands(self, arrays: bool = True):
+        """The island census (include/kaboodle_islands.h): an `Islands` with `summary` (dict of kb_islands) and the
+        uint32 arrays `label` (the lowest id of the id's island, KB_CENSUS_NONE where it does not run) and `size` over
+        all ids (None with arrays=False: the summary alone).  Computed on the device by kb_sim_islands (dense handles,
+        unsharded or in-process shards); a library without it (the CPU oracle) answers the same call through
+        islands.islands_of_sim, so both are compared through identical calls."""
+        if "sim_islands" not in self.lib.fn:
+            from .islands import islands_of_sim
+            return islands_of_sim(self, arrays)
+        from .islands import Islands
+        out = KbIslands()
+        outs, args = _out_arrays(arrays, (["u4"] * 2, self.capacity))
+        self.lib.call("sim_islands", self.h, C.byref(out), *args)
+        return Islands(out.as_dict(), *outs)
+
+    def islands_device_ms(self) -> float:
+        """Device time of the last islands() in ms (kb_sim_islands_device_ms; HIP library only); 0.0 before the
+        first answer."""
+        return self._device_ms("islands")
 
     def snapshot(self) -> bytes:
         """The mesh's state after the last completed round as one byte string (kb_sim_snapshot,

@@ -335,7 +335,7 @@ __global__ __launch_bounds__(256) void k_lat_column(Dev d, uint32_t node, uint16
 }
 
 namespace kb { struct SpSim; }
-enum CensusMs { CM_VIEW, CM_RECIP, CM_CLASSES, CM_LAT, CM_AGE, CM_DELTA, CM_N };   // kb_sim::census_ms (kb_censusframe.h)
+enum CensusMs { CM_VIEW, CM_RECIP, CM_CLASSES, CM_LAT, CM_AGE, CM_DELTA, CM_ISLANDS, CM_N };   // kb_sim::census_ms (kb_censusframe.h)
 
 struct kb_sim {
   kb_config cfg;
@@ -453,6 +453,7 @@ struct kb_sim {
   uint8_t* dl_run = nullptr;           // [C] the running set at the mark
   int32_t dl_round = 0;                // the round of the mark
   uint32_t* dl_buf = nullptr;          // the scratch, allocated by the first delta census
+  uint32_t* is_buf = nullptr;          // the island census's scratch (kb_islands.h), allocated by its first call
 };
 
 // allocation of this handle's device memory; row tables hold the local rows only and their pointer
@@ -2236,6 +2237,9 @@ extern "C" int kb_sim_debug_fold(kb_sim* s, const kb_fold_probe* p) {
 
 // ---- the view-delta census (include/kaboodle_delta.h) -------------------------------------------------------
 #include "kb_delta.h"
+
+// ---- the island census (include/kaboodle_islands.h) ---------------------------------------------------------
+#include "kb_islands.h"
 
 // ---- snapshot and restore (include/kaboodle_snapshot.h) ----------------------------------------------------
 #include "kb_snapshot.h"

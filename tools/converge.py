@@ -17,7 +17,9 @@ views earlier records carry, and beside it the view census's summary (DESIGN.md 
 views also showed: the stale entries and the ghosts (non-running ids some view still holds).  Beside the two it
 records the fingerprint-class census (include/kaboodle_classes.h): its summary and the 8 largest
 classes as (fp, size, rep).  With --track-latency the mesh keeps PeerInfo.latency and the record carries the latency
-census's summary too (include/kaboodle_latency.h).
+census's summary too (include/kaboodle_latency.h).  The island census's summary
+(include/kaboodle_islands.h) goes with them: whether the camps the classes show can still merge (one
+island) or are sealed off from each other (several).
 """
 from __future__ import annotations
 
@@ -121,6 +123,9 @@ def main() -> int:
             recip["fp_classes"] = {"summary": fc.summary, "top_classes": fc.classes.tolist(),
                                    "device_ms": round(m.fp_classes_device_ms(), 4)}
             print(f"[converge {a.mode}] fp classes: {json.dumps(recip['fp_classes'])}", flush=True)
+            # and whether those camps can still reach each other: one island can converge, several cannot
+            recip["islands"] = {"summary": m.islands(arrays=False).summary, "device_ms": round(m.islands_device_ms(), 4)}
+            print(f"[converge {a.mode}] islands: {json.dumps(recip['islands'])}", flush=True)
             if cfg.track_latency:
                 recip["latency_census"] = {"summary": m.latency_census(arrays=False).summary,
                                            "device_ms": round(m.latency_census_device_ms(), 4)}
