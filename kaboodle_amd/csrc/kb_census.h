@@ -5,9 +5,8 @@
 //
 // Dense engine: one streaming pass over the member bits (Dev::bits, [rows][W/32]).  A lane owns one 16-byte
 // column group (4 words = 128 ids) and walks down a tile of rows, so each row read is 1 KiB contiguous per
-// wave.  The column counts are BIT-SLICED: a word of a row is added into 5 bit-planes with a ripple of
-// half adders (plane p holds bit p of 32 vertical counters at once), the 5 planes are added into 12 more
-// every 24 rows, and only at the end of the tile is each of the lane's 128 counters read out of the planes.
+// wave.  The column counts are BIT-SLICED (ColCount<4>, kb_bitpass.h): the 5 low planes are folded into the 12
+// high ones every 24 rows, and only at the end of the tile is each of the lane's 128 counters read out of them.
 // A workgroup's 4 waves (4 row tiles of one column block) combine their counters in LDS and add them to the
 // [W] result with integer atomics: order-free, so the result is deterministic.  The per-row counts (|view|,
 // running members, stale members) come in the same pass: three popcounts per word against loop-invariant
@@ -22,91 +21,51 @@
 
 namespace kb {
 
-constexpr uint32_t CS_LOW = 5, CS_HIGH = 12;      // bit planes: 5 filled row by row, folded into 12 more
-constexpr uint32_t CS_U = 8;                      // rows per batch (16-byte loads in flight per lane)
-constexpr uint32_t CS_FOLD = 24;                  // rows between folds (<= 2^CS_LOW - 1, a multiple of CS_U)
-constexpr uint32_t CS_MAX_RPW = 4080;             // rows per wave (< 2^CS_HIGH, a multiple of CS_FOLD)
+constexpr uint32_t CS_FOLD = 24;                  // rows between folds (<= 2^BP_LOW - 1, a multiple of BP_U)
 constexpr uint32_t CS_COLS = 8192;                // ids per column block: 64 lanes x 128
-constexpr uint32_t CS_LDS = 128 * 65;             // the block's counters: [word of the group][bit][lane], padded
+static_assert(CS_FOLD % BP_U == 0 && CS_FOLD < (1u << BP_LOW) && BP_MAX_RPW % CS_FOLD == 0, "kb_census.h fold period");
 
 struct CsDense {
   uint32_t* kb;                                   // [W] known_by (zeroed)
   uint32_t* rowc;                                 // [3][R] |view|, running members, stale members (zeroed)
-  uint32_t* ab; uint32_t* sb; uint32_t* vb;       // [W/32] running ids, stale-class ids (neither running nor
-                                                  // external), valid ids (< C)
+  IdMasks m;                                      // k_id_masks, all three
   uint32_t rpw;                                   // rows per wave
 };
 
-// the running set as k_alive_bits builds it, and beside it the ids that are neither running nor external
-__global__ void k_cs_masks(Dev d, CsDense a) {
-  const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= d.NWR) return;
-  uint32_t x = 0, s = 0, v = 0;
-  for (uint32_t t = 0; t < 32; ++t) {
-    const uint32_t j = w * 32 + t;
-    if (j >= d.C) break;
-    const bool al = d.alive[j] != 0, ex = d.ext[j] != 0;
-    v |= 1u << t;
-    if (al) x |= 1u << t;
-    if (!al && !ex) s |= 1u << t;
-  }
-  a.ab[w] = x; a.sb[w] = s; a.vb[w] = v;
-}
-
-// x joins the vertical counters of planes p[0..N): a ripple of half adders (the carry out of the top plane
-// is zero while fewer than 2^N words have been added)
-template <uint32_t N> __device__ __attribute__((always_inline)) inline void cs_add1(uint32_t (&p)[N], uint32_t x) {
-#pragma unroll
-  for (uint32_t k = 0; k < N; ++k) { const uint32_t c = p[k] & x; p[k] ^= x; x = c; }
-}
-// the low planes' counters are added to the high planes' (full adders, then the carry's ripple) and cleared
-__device__ __attribute__((always_inline)) inline void cs_fold(uint32_t (&h)[CS_HIGH], uint32_t (&l)[CS_LOW]) {
-  uint32_t c = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < CS_LOW; ++k) {
-    const uint32_t s = h[k] ^ l[k];
-    const uint32_t c2 = (h[k] & l[k]) | (s & c);
-    h[k] = s ^ c; c = c2; l[k] = 0;
-  }
-#pragma unroll
-  for (uint32_t k = CS_LOW; k < CS_HIGH; ++k) { const uint32_t c2 = h[k] & c; h[k] ^= c; c = c2; }
-}
-
 // grid (W / 8192 column blocks, row tiles of 4 x rpw rows), 256 threads
 __global__ __launch_bounds__(256) void k_cs_dense(Dev d, CsDense a) {
-  __shared__ uint32_t cnt[CS_LDS];
-  for (uint32_t k = threadIdx.x; k < CS_LDS; k += 256) cnt[k] = 0;
+  __shared__ uint32_t cnt[col_lds(4)];
+  for (uint32_t k = threadIdx.x; k < col_lds(4); k += 256) cnt[k] = 0;
   __syncthreads();
   const uint32_t l = lane();
   const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const uint32_t nw4 = d.NWR / 4;
   const uint32_t cg = blockIdx.x * 64 + l;                       // this lane's column group (< nw4: the grid is exact)
-  const uint4 ab = reinterpret_cast<const uint4*>(a.ab)[cg];
-  const uint4 sb = reinterpret_cast<const uint4*>(a.sb)[cg];
-  const uint4 vb = reinterpret_cast<const uint4*>(a.vb)[cg];
-  const uint64_t first = (uint64_t)d.lo + (uint64_t)(blockIdx.y * 4 + wv) * a.rpw;
-  const uint32_t r0 = first < d.hi ? (uint32_t)first : d.hi;
-  const uint32_t r1 = d.hi - r0 > a.rpw ? r0 + a.rpw : d.hi;
+  const uint4 ab = reinterpret_cast<const uint4*>(a.m.ab)[cg];
+  const uint4 sb = reinterpret_cast<const uint4*>(a.m.sb)[cg];
+  const uint4 vb = reinterpret_cast<const uint4*>(a.m.vb)[cg];
+  uint32_t r0, r1;
+  wave_rows(d.lo, d.hi, blockIdx.y, wv, a.rpw, r0, r1);
   const uint4* rows = reinterpret_cast<const uint4*>(d.bits);
-  uint32_t lo[4][CS_LOW] = {}, hi[4][CS_HIGH] = {};
+  ColCount<4> cc;
   uint32_t nlow = 0;
-  for (uint32_t r = r0; r < r1; r += CS_U) {
+  for (uint32_t r = r0; r < r1; r += BP_U) {
     uint32_t am = 0;                                             // the batch's running rows: a scalar mask
 #pragma unroll
-    for (uint32_t u = 0; u < CS_U; ++u) if (r + u < r1 && d.alive[r + u]) am |= 1u << u;
+    for (uint32_t u = 0; u < BP_U; ++u) if (r + u < r1 && d.alive[r + u]) am |= 1u << u;
     am = (uint32_t)__builtin_amdgcn_readfirstlane((int)am);
     if (!am) continue;                                           // no running row: nothing is read
-    uint4 v[CS_U];
+    uint4 v[BP_U];
 #pragma unroll
-    for (uint32_t u = 0; u < CS_U; ++u) {                        // every load of the batch before its first use
+    for (uint32_t u = 0; u < BP_U; ++u) {                        // every load of the batch before its first use
       const uint32_t rr = r + u < r1 ? r + u : r1 - 1;
       v[u] = rows[(size_t)rr * nw4 + cg];
     }
 #pragma unroll
-    for (uint32_t u = 0; u < CS_U; ++u) {
+    for (uint32_t u = 0; u < BP_U; ++u) {
       if (!((am >> u) & 1u)) continue;                           // a scalar branch: the row is not an observer
       const uint32_t x0 = v[u].x & vb.x, x1 = v[u].y & vb.y, x2 = v[u].z & vb.z, x3 = v[u].w & vb.w;
-      cs_add1(lo[0], x0); cs_add1(lo[1], x1); cs_add1(lo[2], x2); cs_add1(lo[3], x3);
+      cc.add(0, x0); cc.add(1, x1); cc.add(2, x2); cc.add(3, x3);
       const uint32_t nv = __popc(x0) + __popc(x1) + __popc(x2) + __popc(x3);
       const uint32_t nr = __popc(x0 & ab.x) + __popc(x1 & ab.y) + __popc(x2 & ab.z) + __popc(x3 & ab.w);
       const uint32_t ns = __popc(x0 & sb.x) + __popc(x1 & sb.y) + __popc(x2 & sb.z) + __popc(x3 & sb.w);
@@ -119,30 +78,13 @@ __global__ __launch_bounds__(256) void k_cs_dense(Dev d, CsDense a) {
         if (t1) atomicAdd(&a.rowc[2 * R + k], t1);
       }
     }
-    nlow += CS_U;
-    if (nlow == CS_FOLD) {
-#pragma unroll
-      for (uint32_t q = 0; q < 4; ++q) cs_fold(hi[q], lo[q]);
-      nlow = 0;
-    }
+    nlow += BP_U;
+    if (nlow == CS_FOLD) { cc.fold(); nlow = 0; }
   }
-#pragma unroll
-  for (uint32_t q = 0; q < 4; ++q) cs_fold(hi[q], lo[q]);
-  // the lane's 128 counters out of the planes, into the block's LDS counters (consecutive lanes, consecutive banks)
-  for (uint32_t c = 0; c < 32; ++c) {
-#pragma unroll
-    for (uint32_t q = 0; q < 4; ++q) {
-      uint32_t n = 0;
-#pragma unroll
-      for (uint32_t p = 0; p < CS_HIGH; ++p) n |= ((hi[q][p] >> c) & 1u) << p;
-      if (n) atomicAdd(&cnt[(q * 32 + c) * 65 + l], n);
-    }
-  }
+  cc.fold();
+  cc.readout(cnt, l);
   __syncthreads();
-  for (uint32_t k = threadIdx.x; k < CS_COLS; k += 256) {        // id blockIdx.x * 8192 + k: lane k / 128, word, bit
-    const uint32_t n = cnt[(((k >> 5) & 3u) * 32 + (k & 31u)) * 65 + (k >> 7)];
-    if (n) atomicAdd(&a.kb[(size_t)blockIdx.x * CS_COLS + k], n);
-  }
+  col_flush<4>(cnt, a.kb + (size_t)blockIdx.x * CS_COLS);
 }
 
 // ---- sparse rows ---------------------------------------------------------------------------------------
@@ -223,9 +165,11 @@ struct CsPart {
 static void cs_part_init(CsPart& p, uint32_t C) {
   p.kb.assign(C, 0); p.view.assign(C, 0); p.run.assign(C, 0); p.stale.assign(C, 0); p.held.assign(C, 0);
 }
-// the rows' counts of a shard (device [3][R]) and its known_by land in the part, added to what is there
+// the end of a leaf's pass: its device time, the rows' counts of the shard (device [3][R]) and its known_by join the part
 static int cs_collect(CsPart& p, uint32_t C, uint32_t lo, uint32_t R, const uint32_t* d_kb, const uint32_t* d_rowc,
-                      const uint8_t* d_alive, const uint8_t* d_ext, hipStream_t st) {
+                      const uint8_t* d_alive, const uint8_t* d_ext, hipStream_t st, CsTimer& tm) {
+  tm.stop(st);                                                   // the pass ends here: its launches are all issued
+  HIPCHK(hipGetLastError());
   // sized before the first copy waits for the kernels: zero-filling [C] and [3][R] words overlaps their run
   std::vector<uint32_t> kb(C), rc(3ull * R);
   p.alive.resize(C); p.ext.resize(C);
@@ -234,6 +178,7 @@ static int cs_collect(CsPart& p, uint32_t C, uint32_t lo, uint32_t R, const uint
   HIPCHK(fetch(p.alive, d_alive, C, st));
   HIPCHK(fetch(p.ext, d_ext, C, st));
   HIPCHK(hipStreamSynchronize(st));
+  p.ms += tm.ms();
   for (uint32_t j = 0; j < C; ++j) p.kb[j] += kb[j];
   for (uint32_t k = 0; k < R; ++k) {
     p.view[lo + k] = rc[k]; p.run[lo + k] = rc[R + k]; p.stale[lo + k] = rc[2ull * R + k]; p.held[lo + k] = 1;
@@ -245,53 +190,43 @@ static int cs_collect(CsPart& p, uint32_t C, uint32_t lo, uint32_t R, const uint
 static int cs_leaf(kb_sim* s, CsPart& p) {
   (void)hipSetDevice(s->device);
   const Dev& d = s->d;
-  if (!s->cs_buf) HIPCHK(talloc(s, &s->cs_buf, (size_t)s->W + 3ull * s->R + 3ull * d.NWR));
   CsDense a;
-  // the masks sit right after known_by: both are whole KiB, so the masks' 16-byte loads are aligned for any R
-  a.kb = s->cs_buf; a.ab = a.kb + s->W; a.sb = a.ab + d.NWR; a.vb = a.sb + d.NWR; a.rowc = a.vb + d.NWR;
+  auto lay = [&](Carve& c) {                                     // known_by and the rows' counts are cleared every pass
+    c.zero_from(); a.kb = c.take<uint32_t>(s->W); a.rowc = c.take<uint32_t>(3ull * s->R); c.zero_to();
+    a.m = carve_masks(c, d.NWR, true);
+  };
+  if (!s->cs_buf) HIPCHK(talloc(s, &s->cs_buf, carve_bytes(lay) / 4));
+  const Carve c = carve(s->cs_buf, lay);
+  // env KB_CENSUS_RPW overrides the rows per wave, in whole fold periods (tools/census_cost.py records its value,
+  // DESIGN.md §12)
   const uint32_t cb = s->W / CS_COLS;
-  // rows per wave: about 16 waves a CU (the loads in flight that a streaming pass needs), whole fold periods.
-  // env KB_CENSUS_RPW overrides it: a measurement knob only (tools/census_cost.py records its value, DESIGN.md
-  // §12); results do not depend on it
-  uint64_t rpw = ((uint64_t)s->R * cb + 16ull * s->ncu - 1) / (16ull * s->ncu);
-  if (const char* ev = getenv("KB_CENSUS_RPW")) rpw = (uint64_t)atoll(ev);
-  rpw = std::min<uint64_t>(std::max<uint64_t>((rpw + CS_FOLD - 1) / CS_FOLD * CS_FOLD, CS_FOLD), CS_MAX_RPW);
-  a.rpw = (uint32_t)rpw;
-  const uint32_t tiles = (uint32_t)((s->R + 4 * rpw - 1) / (4 * rpw));
+  a.rpw = rows_per_wave(s->R, cb, s->ncu, rpw_env("KB_CENSUS_RPW"), CS_FOLD, BP_MAX_RPW);
   CsTimer tm;
   if (!tm.start(s->st)) { seterr("census: events"); return KB_IO_ERROR; }
-  HIPCHK(hipMemsetAsync(a.kb, 0, 4ull * ((size_t)s->W + 3ull * d.NWR + 3ull * s->R), s->st));
-  k_cs_masks<<<(d.NWR + 255) / 256, 256, 0, s->st>>>(d, a);
-  k_cs_dense<<<dim3(cb, tiles), 256, 0, s->st>>>(d, a);
-  tm.stop(s->st);
-  HIPCHK(hipGetLastError());
-  const int rc = cs_collect(p, s->C, s->lo, s->R, a.kb, a.rowc, d.alive, d.ext, s->st);
-  if (rc) return rc;
-  p.ms += tm.ms();
-  return KB_OK;
+  HIPCHK(hipMemsetAsync(c.zero_ptr(), 0, c.zero_bytes(), s->st));
+  id_masks(d.alive, d.ext, d.C, d.NWR, a.m, s->st);
+  k_cs_dense<<<dim3(cb, row_tiles(s->R, a.rpw)), 256, 0, s->st>>>(d, a);
+  return cs_collect(p, s->C, s->lo, s->R, a.kb, a.rowc, d.alive, d.ext, s->st, tm);
 }
 // sparse rows (the contact-age census reuses the pass and its scratch, kb_agecensus.h)
 static int cs_leaf(SpSim* S, CsPart& p) {
   (void)hipSetDevice(S->device);
   const SpDev& d = S->d;
   const uint32_t C = S->C, R = S->R;
-  if (!S->cs_buf) {
-    if (sp_alloc(S, &S->cs_buf, 2ull * C + 3ull * R + 4) != hipSuccess) { seterr("census: device allocation failed"); return KB_CAPACITY; }
-  }
   CsSparse a;
-  a.delta = reinterpret_cast<int32_t*>(S->cs_buf); a.acc = S->cs_buf + C; a.rowc = a.acc + 4; a.kb = a.rowc + 3ull * R;
+  auto lay = [&](Carve& c) {                                     // all but known_by is cleared every pass
+    c.zero_from(); a.delta = c.take<int32_t>(C); a.acc = c.take<uint32_t>(4); a.rowc = c.take<uint32_t>(3ull * R); c.zero_to();
+    a.kb = c.take<uint32_t>(C);
+  };
+  if (!S->cs_buf && sp_alloc(S, &S->cs_buf, carve_bytes(lay) / 4) != hipSuccess) { seterr("census: device allocation failed"); return KB_CAPACITY; }
+  const Carve c = carve(S->cs_buf, lay);
   CsTimer tm;
   if (!tm.start(S->st)) { seterr("census: events"); return KB_IO_ERROR; }
-  HIPCHK(hipMemsetAsync(S->cs_buf, 0, 4ull * ((size_t)C + 4 + 3ull * R), S->st));
+  HIPCHK(hipMemsetAsync(c.zero_ptr(), 0, c.zero_bytes(), S->st));
   k_cs_sp_base<<<(C + 255) / 256, 256, 0, S->st>>>(d, a);
   k_cs_sp_rows<<<(R + 255) / 256, 256, 0, S->st>>>(d, a);
   k_cs_sp_finish<<<(C + 255) / 256, 256, 0, S->st>>>(d, a);
-  tm.stop(S->st);
-  HIPCHK(hipGetLastError());
-  const int rc = cs_collect(p, C, S->lo, R, a.kb, a.rowc, d.alive, d.ext, S->st);
-  if (rc) return rc;
-  p.ms += tm.ms();
-  return KB_OK;
+  return cs_collect(p, C, S->lo, R, a.kb, a.rowc, d.alive, d.ext, S->st, tm);
 }
 
 // the O(ids) reductions of the summary, on the host

@@ -1,7 +1,8 @@
-// kb_censusframe.h — the host frame the five censuses share (DESIGN.md "Host control plane"): argument and handle
-// checks, the device-time figures, scratch that grows, the download into host vectors and the copy into the caller's
-// arrays.  A census supplies its kernels, its *Part, its leaf overloads on kb_sim* / SpSim* and its summary; the
-// rest is here, once.  Included by kb_sim.hip after kb_ctl.h, before the census headers.
+// kb_censusframe.h — the host frame the seven censuses share (view, reciprocity, classes, latency, contact age, delta,
+// islands; DESIGN.md "Host control plane"): argument and handle checks, the device-time figures, scratch that grows,
+// the download into host vectors and the copy into the caller's arrays.  A census supplies its kernels, its *Part, its
+// leaf overloads on kb_sim* / SpSim* and its summary; the rest is here, once.  Its other half: kb_bitpass.h (device)
+// and kb_scratch.h (scratch carver, rows-per-wave plan).  Included by kb_sim.hip after kb_ctl.h, before both.
 #pragma once
 
 // the first pointer that is set (nullptr: the caller asked for none of these arrays)

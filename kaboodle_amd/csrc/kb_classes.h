@@ -254,30 +254,28 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_lookup(FcArgs a) {
 }  // namespace kb
 
 // ---- host side -------------------------------------------------------------------------------------------
-// the scratch of a census over n rows: byte offsets into one allocation, every one a multiple of 16
+// the scratch of a census over n rows, laid out by fc_lay: every part 16-byte aligned
 struct FcPlan {
   uint32_t n = 0, T = 0, tiles = 0;
-  size_t tab = 0, cand_a = 0, cand_b = 0, list = 0, rep = 0, size = 0, fp = 0, run = 0, bytes = 0;
+  uint32_t* acc = nullptr; FcSlot* tab = nullptr;   // the summary words and the table: cleared before every census
+  unsigned long long* cand_a = nullptr; unsigned long long* cand_b = nullptr;
+  kb_fp_class* list = nullptr;
+  uint32_t* rep = nullptr; uint32_t* size = nullptr; uint32_t* fp = nullptr; uint8_t* run = nullptr;
 };
 static bool fc_plan(size_t n, FcPlan& p) {
   if (n > (1u << 30)) return false;
   size_t T = FC_TILE;
   while (T < 2 * n) T <<= 1;
-  const size_t n16 = (n + 15) & ~(size_t)15;
   p.n = (uint32_t)n; p.T = (uint32_t)T; p.tiles = (uint32_t)(T / FC_TILE);
-  size_t o = 256;                                   // the summary words
-  p.tab = o; o += sizeof(FcSlot) * T;
-  p.cand_a = o; o += 8ull * FC_K * p.tiles;
-  p.cand_b = o; o += 8ull * FC_K * ((p.tiles + 3) / 4);
-  p.list = o; o += sizeof(kb_fp_class) * FC_K;
-  p.rep = o; o += 4 * n16;
-  p.size = o; o += 4 * n16;
-  p.fp = o; o += 4 * n16;
-  p.run = o; o += n16;
-  p.bytes = o;
   return true;
 }
-static_assert(FA_WORDS * 4 <= 256 && sizeof(kb_fp_class) == 16, "kb_classes.h scratch layout");
+static void fc_lay(Carve& c, FcPlan& p) {
+  c.zero_from(); p.acc = c.take<uint32_t>(FA_WORDS, 16); p.tab = c.take<FcSlot>(p.T, 16); c.zero_to();
+  p.cand_a = c.take<unsigned long long>((size_t)FC_K * p.tiles, 16); p.cand_b = c.take<unsigned long long>((size_t)FC_K * ((p.tiles + 3) / 4), 16);
+  p.list = c.take<kb_fp_class>(FC_K, 16);
+  p.rep = c.take<uint32_t>(p.n, 16); p.size = c.take<uint32_t>(p.n, 16); p.fp = c.take<uint32_t>(p.n, 16); p.run = c.take<uint8_t>(p.n, 16);
+}
+static_assert(sizeof(kb_fp_class) == 16, "kb_classes.h scratch layout");
 
 struct FcSeg { const uint32_t* src; uint32_t lo, n; };            // a shard's fingerprints: rows [lo, lo + n)
 
@@ -289,37 +287,34 @@ static int fc_check(const void* out, const kb_fp_class* list, size_t cap_list, c
   return census_caps(who, out, nullptr, 0, 0, any_of(rep, size), cap_rows, n);
 }
 
-// The census over d_fp / d_run ([n], device) in scratch `buf` laid out by `p`, on stream st.  With `segs` the
+// The census over d_fp / d_run ([n], device) in the scratch laid out in `c` by fc_lay(c, p), on stream st.  With `segs` the
 // fingerprints are first gathered from the shards into the scratch (inside the timed span).
-static int fc_exec(void* buf, const FcPlan& p, hipStream_t st, const uint32_t* d_fp, const uint8_t* d_run,
+static int fc_exec(const Carve& c, const FcPlan& p, hipStream_t st, const uint32_t* d_fp, const uint8_t* d_run,
                    const std::vector<FcSeg>* segs, uint32_t true_fp, int32_t round, kb_fp_classes* out, kb_fp_class* list,
                    size_t cap_list, size_t* n_list, uint32_t* rep, uint32_t* size, double* ms) {
-  char* b = static_cast<char*>(buf);
   FcArgs a{};
-  a.n = p.n; a.acc = reinterpret_cast<uint32_t*>(b); a.tab = reinterpret_cast<FcSlot*>(b + p.tab); a.mask = p.T - 1;
+  a.n = p.n; a.acc = p.acc; a.tab = p.tab; a.mask = p.T - 1;
   a.true_fp = true_fp; a.want_list = cap_list > 0;
-  a.cand = reinterpret_cast<unsigned long long*>(b + p.cand_a);
-  a.rep = reinterpret_cast<uint32_t*>(b + p.rep); a.size = reinterpret_cast<uint32_t*>(b + p.size);
+  a.cand = p.cand_a; a.rep = p.rep; a.size = p.size;
   a.fp = d_fp; a.run = d_run;
   CsTimer tm;
   if (!tm.start(st)) { seterr("fp_classes: events"); return KB_IO_ERROR; }
   if (segs) {
-    uint32_t* g = reinterpret_cast<uint32_t*>(b + p.fp);
     for (const FcSeg& sg : *segs)
-      if (sg.n) HIPCHK(hipMemcpyAsync(g + sg.lo, sg.src, 4ull * sg.n, hipMemcpyDeviceToDevice, st));
-    a.fp = g;
+      if (sg.n) HIPCHK(hipMemcpyAsync(p.fp + sg.lo, sg.src, 4ull * sg.n, hipMemcpyDeviceToDevice, st));
+    a.fp = p.fp;
   }
-  HIPCHK(hipMemsetAsync(b, 0, p.tab + sizeof(FcSlot) * (size_t)p.T, st));
+  HIPCHK(hipMemsetAsync(c.zero_ptr(), 0, c.zero_bytes(), st));
   if (p.n) k_fc_count<<<(p.n + FC_ROWS - 1) / FC_ROWS, FC_THREADS, 0, st>>>(a);
   k_fc_scan<<<p.tiles, FC_THREADS, 0, st>>>(a);
   if (cap_list) {
     unsigned long long* src = a.cand;
-    unsigned long long* dst = reinterpret_cast<unsigned long long*>(b + p.cand_b);
+    unsigned long long* dst = p.cand_b;
     for (uint32_t nblk = p.tiles; nblk > 1; nblk = (nblk + 3) / 4) {
       k_fc_merge<<<(nblk + 3) / 4, FC_THREADS, 0, st>>>(src, nblk, dst);
       std::swap(src, dst);
     }
-    k_fc_list<<<(uint32_t)(cap_list + 255) / 256, 256, 0, st>>>(a, src, (uint32_t)cap_list, reinterpret_cast<uint4*>(b + p.list));
+    k_fc_list<<<(uint32_t)(cap_list + 255) / 256, 256, 0, st>>>(a, src, (uint32_t)cap_list, reinterpret_cast<uint4*>(p.list));
   }
   if ((rep || size) && p.n) k_fc_lookup<<<(p.n + FC_THREADS - 1) / FC_THREADS, FC_THREADS, 0, st>>>(a);
   tm.stop(st);
@@ -327,7 +322,7 @@ static int fc_exec(void* buf, const FcPlan& p, hipStream_t st, const uint32_t* d
   uint32_t acc[FA_WORDS];
   std::vector<kb_fp_class> got;
   HIPCHK(hipMemcpyAsync(acc, a.acc, sizeof acc, hipMemcpyDeviceToHost, st));
-  HIPCHK(fetch(got, b + p.list, cap_list, st));
+  HIPCHK(fetch(got, p.list, cap_list, st));
   if (rep && p.n) HIPCHK(hipMemcpyAsync(rep, a.rep, 4ull * p.n, hipMemcpyDeviceToHost, st));
   if (size && p.n) HIPCHK(hipMemcpyAsync(size, a.size, 4ull * p.n, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -365,12 +360,14 @@ extern "C" int kb_sim_fp_classes(kb_sim* s, kb_fp_classes* out, kb_fp_class* lis
   FcPlan p;
   if (!fc_plan(s->C, p)) { seterr("kb_sim_fp_classes: capacity above 2^30"); return KB_CAPACITY; }
   // the scratch belongs to the engine whose stream runs the census (it is released with that engine)
-  { const int rc = route(s, R_FIRST, 0, [&](auto* e) { return eng_grow(e, &s->fc_buf, &s->fc_cap, p.bytes); }); if (rc) return rc; }
+  auto lay = [&](Carve& c) { fc_lay(c, p); };
+  { const int rc = route(s, R_FIRST, 0, [&](auto* e) { return eng_grow(e, &s->fc_buf, &s->fc_cap, carve_bytes(lay)); }); if (rc) return rc; }
+  const Carve c = carve(s->fc_buf, lay);
   std::vector<FcSeg> segs;
   if (grp) route(s, R_ALL, 0, [&](auto* e) { segs.push_back(FcSeg{eng_fp(e) + e->lo, e->lo, e->R}); return KB_OK; });
   // the first shard's stream runs the census; every shard is on its device
   return route(s, R_FIRST, 0, [&](auto* e) {
-    return fc_exec(s->fc_buf, p, eng_stream(e), eng_fp(e), eng_alive(e), grp ? &segs : nullptr, tfp, e->round, out, list, cap_list,
+    return fc_exec(c, p, eng_stream(e), eng_fp(e), eng_alive(e), grp ? &segs : nullptr, tfp, e->round, out, list, cap_list,
                    n_list, rep, size, &s->census_ms[CM_CLASSES]);
   });
 }
@@ -386,12 +383,12 @@ extern "C" int kb_fp_classes_of(int device, const uint32_t* fps, const uint8_t* 
   { const int rc = o.open(device, "kb_fp_classes_of"); if (rc) return rc; }
   FcPlan p;
   if (!fc_plan(n, p)) { seterr("kb_fp_classes_of: more than 2^30 rows"); return KB_CAPACITY; }
-  { const int rc = dev_reserve(&o.buf, &o.cap, p.bytes, "fp_classes: scratch allocation failed"); if (rc) return rc; }
-  char* b = static_cast<char*>(o.buf);
+  auto lay = [&](Carve& c) { fc_lay(c, p); };
+  { const int rc = dev_reserve(&o.buf, &o.cap, carve_bytes(lay), "fp_classes: scratch allocation failed"); if (rc) return rc; }
+  const Carve c = carve(o.buf, lay);
   if (n) {
-    HIPCHK(hipMemcpyAsync(b + p.fp, fps, 4 * n, hipMemcpyHostToDevice, o.st));
-    HIPCHK(hipMemcpyAsync(b + p.run, running, n, hipMemcpyHostToDevice, o.st));
+    HIPCHK(hipMemcpyAsync(p.fp, fps, 4 * n, hipMemcpyHostToDevice, o.st));
+    HIPCHK(hipMemcpyAsync(p.run, running, n, hipMemcpyHostToDevice, o.st));
   }
-  return fc_exec(o.buf, p, o.st, reinterpret_cast<const uint32_t*>(b + p.fp), reinterpret_cast<const uint8_t*>(b + p.run), nullptr,
-                 true_fp, -1, out, list, cap_list, n_list, rep, size, nullptr);
+  return fc_exec(c, p, o.st, p.fp, p.run, nullptr, true_fp, -1, out, list, cap_list, n_list, rep, size, nullptr);
 }

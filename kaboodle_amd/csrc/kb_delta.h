@@ -1,6 +1,6 @@
 // kb_delta.h — the view-delta census (include/kaboodle_delta.h): what every view gained and lost
 // since a mark.  Included at the end of kb_sim.hip beside the other censuses; stands on the frame of
-// kb_censusframe.h and on the bit-plane adders of kb_census.h.
+// kb_censusframe.h and kb_bitpass.h (the id masks, the column counters, the row tiles and their plan).
 //
 // A baseline is a copy of the member bits of a handle's rows ([rows][W/32]) and of the running set, taken by
 // kb_sim_delta_mark.  The census is ONE streaming pass over the current bits and the baseline, shaped like
@@ -22,71 +22,42 @@
 namespace kb {
 
 constexpr uint32_t DL_COLS = 4096;                // ids per column block: 64 lanes x 64
-constexpr uint32_t DL_LDS = 64 * 65;              // one set's counters of a block: [word of the group][bit][lane], padded
-constexpr uint32_t DL_LOW_MAX = (1u << CS_LOW) - 1;   // rows the low planes hold between folds
-constexpr uint32_t DL_MAX_RPW = 4080;             // rows per wave (< 2^CS_HIGH, a multiple of CS_U)
+constexpr uint32_t DL_LOW_MAX = (1u << BP_LOW) - 1;   // rows the low planes hold between folds
 
 struct DlArgs {
   const uint32_t* now;                            // [R][NWR] the rows' member bits (row 0 is id lo)
   uint32_t* base;                                 // [R][NWR] the baseline; written under advance only
   const uint8_t* run_now;                         // [C] running now, per id
   const uint8_t* run_base;                        // [C] running at the mark, per id
-  uint32_t* ab; uint32_t* vb;                     // [NWR] ids running now, valid ids (< C): written by k_dl_masks
+  IdMasks m;                                      // k_id_masks over run_now: ab and vb
   uint32_t* gby; uint32_t* lby;                   // [W] gained_by, lost_by (zeroed)
   uint32_t* rowc;                                 // [3][R] gained, lost, lost_live (zeroed)
   uint32_t C, NWR, lo, R;
-  uint32_t rpw;                                   // rows per wave: a multiple of CS_U, <= DL_MAX_RPW
+  uint32_t rpw;                                   // rows per wave: a multiple of BP_U, <= BP_MAX_RPW
   uint32_t advance;                               // baseline := now in the same pass
 };
 
-__global__ void k_dl_masks(DlArgs a) {
-  const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= a.NWR) return;
-  uint32_t x = 0, v = 0;
-  for (uint32_t t = 0; t < 32; ++t) {
-    const uint32_t j = w * 32 + t;
-    if (j >= a.C) break;
-    v |= 1u << t;
-    if (a.run_now[j]) x |= 1u << t;
-  }
-  a.ab[w] = x; a.vb[w] = v;
-}
-
-// a lane's counters out of the high planes into the block's LDS counters (consecutive lanes, consecutive banks)
-__device__ __attribute__((always_inline)) inline void dl_readout(uint32_t* cnt, const uint32_t (&hi)[2][CS_HIGH], uint32_t l) {
-  for (uint32_t c = 0; c < 32; ++c) {
-#pragma unroll
-    for (uint32_t q = 0; q < 2; ++q) {
-      uint32_t n = 0;
-#pragma unroll
-      for (uint32_t p = 0; p < CS_HIGH; ++p) n |= ((hi[q][p] >> c) & 1u) << p;
-      if (n) atomicAdd(&cnt[(q * 32 + c) * 65 + l], n);
-    }
-  }
-}
-
 // grid (W / 4096 column blocks, row tiles of 4 x rpw rows), 256 threads
 __global__ __launch_bounds__(256) void k_delta(DlArgs a) {
-  __shared__ uint32_t cnt[2][DL_LDS];
-  for (uint32_t k = threadIdx.x; k < 2 * DL_LDS; k += 256) (&cnt[0][0])[k] = 0;
+  __shared__ uint32_t cnt[2][col_lds(2)];
+  for (uint32_t k = threadIdx.x; k < 2 * col_lds(2); k += 256) (&cnt[0][0])[k] = 0;
   __syncthreads();
   const uint32_t l = lane();
   const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const uint32_t nw2 = a.NWR / 2;
   const uint32_t cg = blockIdx.x * 64 + l;                       // this lane's column group (< nw2: the grid is exact)
-  const uint2 ab = reinterpret_cast<const uint2*>(a.ab)[cg];
-  const uint2 vb = reinterpret_cast<const uint2*>(a.vb)[cg];
-  const uint64_t first = (uint64_t)(blockIdx.y * 4 + wv) * a.rpw;
-  const uint32_t r0 = first < a.R ? (uint32_t)first : a.R;       // local rows [r0, r1) of [0, R)
-  const uint32_t r1 = a.R - r0 > a.rpw ? r0 + a.rpw : a.R;
+  const uint2 ab = reinterpret_cast<const uint2*>(a.m.ab)[cg];
+  const uint2 vb = reinterpret_cast<const uint2*>(a.m.vb)[cg];
+  uint32_t r0, r1;                                               // local rows [r0, r1) of [0, R)
+  wave_rows(0, a.R, blockIdx.y, wv, a.rpw, r0, r1);
   const uint2* now = reinterpret_cast<const uint2*>(a.now);
   uint2* base = reinterpret_cast<uint2*>(a.base);
-  uint32_t glo[2][CS_LOW] = {}, ghi[2][CS_HIGH] = {}, llo[2][CS_LOW] = {}, lhi[2][CS_HIGH] = {};
+  ColCount<2> gain, loss;                                        // the columns' gained_by and lost_by
   uint32_t nlow = 0;                                             // rows in the low planes: wave-uniform
-  for (uint32_t r = r0; r < r1; r += CS_U) {
+  for (uint32_t r = r0; r < r1; r += BP_U) {
     uint32_t cm = 0, nm = 0;                                     // the batch's continuing rows, new rows: scalar masks
 #pragma unroll
-    for (uint32_t u = 0; u < CS_U; ++u) {
+    for (uint32_t u = 0; u < BP_U; ++u) {
       if (r + u >= r1) continue;
       const bool rn = a.run_now[a.lo + r + u] != 0, rb = a.run_base[a.lo + r + u] != 0;
       if (rn && rb) cm |= 1u << u;
@@ -96,13 +67,13 @@ __global__ __launch_bounds__(256) void k_delta(DlArgs a) {
     nm = (uint32_t)__builtin_amdgcn_readfirstlane((int)nm);
     if (a.advance && nm) {                                       // a row that began to run: its bits become its baseline
 #pragma unroll
-      for (uint32_t u = 0; u < CS_U; ++u)
+      for (uint32_t u = 0; u < BP_U; ++u)
         if ((nm >> u) & 1u) base[(size_t)(r + u) * nw2 + cg] = now[(size_t)(r + u) * nw2 + cg];
     }
     if (!cm) continue;                                           // no continuing row: nothing is read
-    uint2 vn[CS_U], vo[CS_U];
+    uint2 vn[BP_U], vo[BP_U];
 #pragma unroll
-    for (uint32_t u = 0; u < CS_U; ++u) {                        // every load of the batch before its first use
+    for (uint32_t u = 0; u < BP_U; ++u) {                        // every load of the batch before its first use
       vn[u] = vo[u] = make_uint2(0u, 0u);
       if ((cm >> u) & 1u) {                                      // a scalar branch: other rows are not read
         vn[u] = now[(size_t)(r + u) * nw2 + cg];
@@ -110,14 +81,14 @@ __global__ __launch_bounds__(256) void k_delta(DlArgs a) {
       }
     }
 #pragma unroll
-    for (uint32_t u = 0; u < CS_U; ++u) {
+    for (uint32_t u = 0; u < BP_U; ++u) {
       if (!((cm >> u) & 1u)) continue;
       const uint32_t d0 = vn[u].x ^ vo[u].x, d1 = vn[u].y ^ vo[u].y;
       if (a.advance && (d0 | d1)) base[(size_t)(r + u) * nw2 + cg] = vn[u];   // only the groups that differ
       const uint32_t g0 = d0 & vn[u].x & vb.x, g1 = d1 & vn[u].y & vb.y;
       const uint32_t l0 = d0 & vo[u].x & vb.x, l1 = d1 & vo[u].y & vb.y;
       if (__ballot((g0 | g1 | l0 | l1) != 0u) == 0ull) continue;  // wave-uniform: the row changed nothing in this block
-      cs_add1(glo[0], g0); cs_add1(glo[1], g1); cs_add1(llo[0], l0); cs_add1(llo[1], l1);
+      gain.add(0, g0); gain.add(1, g1); loss.add(0, l0); loss.add(1, l1);
       const uint32_t ng = __popc(g0) + __popc(g1), nl = __popc(l0) + __popc(l1);
       const uint32_t nv = __popc(l0 & ab.x) + __popc(l1 & ab.y);
       const uint32_t t0 = wave_sum(ng | (nl << 16));             // <= 4096 each per wave: 16 bits hold them
@@ -128,24 +99,15 @@ __global__ __launch_bounds__(256) void k_delta(DlArgs a) {
         if (t0 >> 16) atomicAdd(&a.rowc[(size_t)a.R + k], t0 >> 16);
         if (t1) atomicAdd(&a.rowc[2 * (size_t)a.R + k], t1);
       }
-      if (++nlow == DL_LOW_MAX) {
-#pragma unroll
-        for (uint32_t q = 0; q < 2; ++q) { cs_fold(ghi[q], glo[q]); cs_fold(lhi[q], llo[q]); }
-        nlow = 0;
-      }
+      if (++nlow == DL_LOW_MAX) { gain.fold(); loss.fold(); nlow = 0; }
     }
   }
-#pragma unroll
-  for (uint32_t q = 0; q < 2; ++q) { cs_fold(ghi[q], glo[q]); cs_fold(lhi[q], llo[q]); }
-  dl_readout(cnt[0], ghi, l);
-  dl_readout(cnt[1], lhi, l);
+  gain.fold(); loss.fold();
+  gain.readout(cnt[0], l);
+  loss.readout(cnt[1], l);
   __syncthreads();
-  for (uint32_t k = threadIdx.x; k < DL_COLS; k += 256) {        // id blockIdx.x * 4096 + k: lane k / 64, word, bit
-    const uint32_t at = (((k >> 5) & 1u) * 32 + (k & 31u)) * 65 + (k >> 6);
-    const uint32_t ng = cnt[0][at], nl = cnt[1][at];
-    if (ng) atomicAdd(&a.gby[(size_t)blockIdx.x * DL_COLS + k], ng);
-    if (nl) atomicAdd(&a.lby[(size_t)blockIdx.x * DL_COLS + k], nl);
-  }
+  col_flush<2>(cnt[0], a.gby + (size_t)blockIdx.x * DL_COLS);
+  col_flush<2>(cnt[1], a.lby + (size_t)blockIdx.x * DL_COLS);
 }
 
 }  // namespace kb
@@ -161,28 +123,22 @@ struct DlPart {
 static void dl_part_init(DlPart& p, size_t C) {
   p.gby.assign(C, 0); p.lby.assign(C, 0); p.gained.assign(C, 0); p.lost.assign(C, 0); p.live.assign(C, 0);
 }
-// words of the pass's scratch: gained_by, lost_by, the two masks, the rows' counts (the first two and the last are
-// cleared before every pass; whole KiB in front of the masks, so their 8-byte loads are aligned)
-static size_t dl_scratch_words(uint32_t W, uint32_t R) { return 2ull * W + 2ull * (W / 32) + 3ull * R; }
-// rows per wave: about 16 waves a CU (the loads in flight that a streaming pass needs).  want != 0 overrides it;
-// whole batches, at most DL_MAX_RPW, and few enough row tiles for one grid
-static uint32_t dl_rpw(uint32_t R, uint32_t W, uint32_t ncu, uint64_t want) {
-  uint64_t rpw = want ? want : ((uint64_t)R * (W / kb::DL_COLS) + 16ull * ncu - 1) / (16ull * ncu);
-  rpw = std::min<uint64_t>(std::max<uint64_t>((rpw + kb::CS_U - 1) / kb::CS_U * kb::CS_U, kb::CS_U), kb::DL_MAX_RPW);
-  while (rpw < kb::DL_MAX_RPW && ((uint64_t)R + 4 * rpw - 1) / (4 * rpw) > 65535) rpw = std::min<uint64_t>(rpw * 2, kb::DL_MAX_RPW);
-  return (uint32_t)rpw;
+// the pass's scratch (a.R, a.NWR set): the results, cleared before every pass, then the masks; the rows per wave
+static void dl_lay(Carve& c, kb::DlArgs& a, uint32_t W, uint32_t ncu, uint64_t want_rpw) {
+  c.zero_from(); a.gby = c.take<uint32_t>(W); a.lby = c.take<uint32_t>(W); a.rowc = c.take<uint32_t>(3ull * a.R); c.zero_to();
+  a.m = carve_masks(c, a.NWR, false);
+  a.rpw = rows_per_wave(a.R, W / kb::DL_COLS, ncu, want_rpw, kb::BP_U, kb::BP_MAX_RPW);
 }
 
-// The pass over a.now / a.base with the running sets a.run_now / a.run_base, scratch at `buf`, on stream st; its
-// results join `p`, the rows' at index a.lo onwards.
-static int dl_exec(uint32_t* buf, kb::DlArgs a, uint32_t W, hipStream_t st, DlPart& p) {
+// The pass over a.now / a.base with the running sets a.run_now / a.run_base, scratch laid out in `c` by dl_lay, on
+// stream st; its results join `p`, the rows' at index a.lo onwards.
+static int dl_exec(const Carve& c, const kb::DlArgs& a, uint32_t W, hipStream_t st, DlPart& p) {
   const uint32_t C = a.C, R = a.R;
-  a.gby = buf; a.lby = a.gby + W; a.ab = a.lby + W; a.vb = a.ab + a.NWR; a.rowc = a.vb + a.NWR;
   CsTimer tm;
   if (!tm.start(st)) { seterr("delta census: events"); return KB_IO_ERROR; }
-  HIPCHK(hipMemsetAsync(buf, 0, 4ull * dl_scratch_words(W, R), st));
-  k_dl_masks<<<(a.NWR + 255) / 256, 256, 0, st>>>(a);
-  if (R) k_delta<<<dim3(W / kb::DL_COLS, (uint32_t)(((uint64_t)R + 4ull * a.rpw - 1) / (4ull * a.rpw))), 256, 0, st>>>(a);
+  HIPCHK(hipMemsetAsync(c.zero_ptr(), 0, c.zero_bytes(), st));
+  id_masks(a.run_now, nullptr, C, a.NWR, a.m, st);
+  if (R) k_delta<<<dim3(W / kb::DL_COLS, row_tiles(R, a.rpw)), 256, 0, st>>>(a);
   tm.stop(st);
   HIPCHK(hipGetLastError());
   std::vector<uint32_t> gby(C), lby(C), rc(3ull * R);            // sized before the first copy waits for the kernels
@@ -265,16 +221,15 @@ static bool dl_marked(SpSim*) { return false; }
 static int dl_leaf(kb_sim* s, bool advance, int32_t* round_base, DlPart& p) {
   (void)hipSetDevice(s->device);
   const Dev& d = s->d;
-  if (!s->dl_buf) HIPCHK(talloc(s, &s->dl_buf, dl_scratch_words(s->W, s->R)));
   kb::DlArgs a{};
   a.now = d.bits + (size_t)s->lo * d.NWR; a.base = s->dl_base; a.run_now = d.alive; a.run_base = s->dl_run;
   a.C = s->C; a.NWR = d.NWR; a.lo = s->lo; a.R = s->R; a.advance = advance;
-  // env KB_DELTA_RPW overrides the rows per wave: a measurement knob only (tools/delta_census_cost.py records its
-  // value); results do not depend on it
-  const char* ev = getenv("KB_DELTA_RPW");
-  a.rpw = dl_rpw(s->R, s->W, s->ncu, ev ? (uint64_t)std::max<long long>(atoll(ev), 1) : 0);
+  // env KB_DELTA_RPW overrides the rows per wave (tools/delta_census_cost.py records its value)
+  auto lay = [&](Carve& c) { dl_lay(c, a, s->W, s->ncu, rpw_env("KB_DELTA_RPW")); };
+  if (!s->dl_buf) HIPCHK(talloc(s, &s->dl_buf, carve_bytes(lay) / 4));
+  const Carve c = carve(s->dl_buf, lay);
   *round_base = s->dl_round;
-  const int rc = dl_exec(s->dl_buf, a, s->W, s->st, p);
+  const int rc = dl_exec(c, a, s->W, s->st, p);
   if (rc) return rc;
   if (p.ext.empty()) {                                           // replicated: the first leaf's copy
     HIPCHK(fetch(p.ext, d.ext, s->C, s->st));
@@ -342,25 +297,26 @@ extern "C" int kb_delta_of(int device, const uint32_t* bits_base, const uint8_t*
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) != hipSuccess) { seterr("kb_delta_of: hipGetDeviceProperties failed"); return KB_NO_DEVICE; }
   const uint32_t C = (uint32_t)capacity, R = (uint32_t)rows, W = (C + 8191) / 8192 * 8192, NWR = W / 32;
-  // the scratch first (whole KiB in front of its masks), then the two bit tables (whole KiB each row), then the flags
-  const size_t scr_b = 4ull * dl_scratch_words(W, R), o_now = (scr_b + 255) & ~(size_t)255, bits_b = 4ull * R * NWR,
-               o_base = o_now + bits_b, o_rn = o_base + bits_b, o_rb = o_rn + C;
-  { const int rc = dev_reserve(&o.buf, &o.cap, o_rb + C, "kb_delta_of: device allocation failed"); if (rc) return rc; }
-  char* b = static_cast<char*>(o.buf);
-  if (bits_b) {
-    HIPCHK(hipMemcpyAsync(b + o_now, bits_now, bits_b, hipMemcpyHostToDevice, o.st));
-    HIPCHK(hipMemcpyAsync(b + o_base, bits_base, bits_b, hipMemcpyHostToDevice, o.st));
-  }
-  HIPCHK(hipMemcpyAsync(b + o_rn, run_now, C, hipMemcpyHostToDevice, o.st));
-  HIPCHK(hipMemcpyAsync(b + o_rb, run_base, C, hipMemcpyHostToDevice, o.st));
   kb::DlArgs a{};
-  a.now = reinterpret_cast<const uint32_t*>(b + o_now); a.base = reinterpret_cast<uint32_t*>(b + o_base);
-  a.run_now = reinterpret_cast<const uint8_t*>(b + o_rn); a.run_base = reinterpret_cast<const uint8_t*>(b + o_rb);
   a.C = C; a.NWR = NWR; a.lo = (uint32_t)row_lo; a.R = R; a.advance = 0;
-  a.rpw = dl_rpw(R, W, (uint32_t)prop.multiProcessorCount, rpw);
+  const size_t bits_n = (size_t)R * NWR;
+  uint32_t* now = nullptr; uint8_t* rn = nullptr; uint8_t* rb = nullptr;
+  auto lay = [&](Carve& c) {                      // the scratch, the two bit tables (8-byte loads), the flags
+    dl_lay(c, a, W, (uint32_t)prop.multiProcessorCount, rpw);
+    now = c.take<uint32_t>(bits_n, 8); a.base = c.take<uint32_t>(bits_n, 8); rn = c.take<uint8_t>(C); rb = c.take<uint8_t>(C);
+  };
+  { const int rc = dev_reserve(&o.buf, &o.cap, carve_bytes(lay), "kb_delta_of: device allocation failed"); if (rc) return rc; }
+  const Carve c = carve(o.buf, lay);
+  a.now = now; a.run_now = rn; a.run_base = rb;
+  if (bits_n) {
+    HIPCHK(hipMemcpyAsync(now, bits_now, 4 * bits_n, hipMemcpyHostToDevice, o.st));
+    HIPCHK(hipMemcpyAsync(a.base, bits_base, 4 * bits_n, hipMemcpyHostToDevice, o.st));
+  }
+  HIPCHK(hipMemcpyAsync(rn, run_now, C, hipMemcpyHostToDevice, o.st));
+  HIPCHK(hipMemcpyAsync(rb, run_base, C, hipMemcpyHostToDevice, o.st));
   DlPart p;
   dl_part_init(p, C);
-  { const int rc = dl_exec(reinterpret_cast<uint32_t*>(b), a, W, o.st, p); if (rc) return rc; }
+  { const int rc = dl_exec(c, a, W, o.st, p); if (rc) return rc; }
   p.ext.assign(external, external + C);
   dl_summary(p, -1, -1, out);
   dl_deliver(p, gained_by, lost_by, gained, lost, lost_live);

@@ -1,6 +1,6 @@
 // kb_islands.h — the island census (include/kaboodle_islands.h): the connected components of the
 // "i holds j" graph over the running peers, each labelled with its lowest id.  Included at the end of kb_sim.hip
-// beside the other censuses; stands on the frame of kb_censusframe.h and on k_cs_masks of kb_census.h.  It reads the
+// beside the other censuses; stands on the frame of kb_censusframe.h and kb_bitpass.h (masks, row table).  It reads the
 // member bits and the running set only (never the stamps or the latency table) and writes only its own scratch.
 //
 // Labels: L[j] = j for a running id, KB_CENSUS_NONE otherwise.  A SWEEP is two launches.  k_is_words jumps every
@@ -29,41 +29,29 @@
 
 namespace kb {
 
-constexpr uint32_t IS_SHARDS = 8;                 // XMAX
 constexpr uint32_t IS_STEP_WORDS = 256;           // words a wave reads per step: 64 lanes x 16 bytes = 8192 ids
 constexpr uint32_t IS_DENSE = 8;                  // members of a word from which its 32 labels are read in 16-byte loads
 
 struct IsArgs {
-  const uint32_t* bits[IS_SHARDS];                // every shard's member bits (biased: indexed by global row)
-  uint32_t lo[IS_SHARDS];                         // its first row; 0xFFFFFFFF for unused entries
-  const uint32_t* ab; const uint32_t* vb;         // [NWR] running ids, valid ids (k_cs_masks)
+  BitRows rows;                                   // rows.C ids, rows.NWR = W/32 words a row (whole IS_STEP_WORDS)
+  IdMasks m;                                      // k_id_masks: ab and vb
   uint32_t* L;                                    // [W] labels
   uint32_t* wmin; uint32_t* wmax;                 // [NWR] per word: min / max label over its running ids
   uint32_t* rown;                                 // [C] entries of each running row (zeroed)
   uint32_t* changed;                              // [1] the sweep lowered a label
-  uint32_t C, NWR;                                // capacity, words per row (W/32, a multiple of IS_STEP_WORDS)
 };
-
-// the shard that holds row r: the last entry whose first row is <= r (lo[] ascending, lo[0] = 0, unused 0xFFFFFFFF:
-// kb_sim_islands checks that before it launches)
-__device__ __attribute__((always_inline)) inline const uint32_t* is_row(const IsArgs& a, uint32_t r) {
-  const uint32_t* p = a.bits[0];
-#pragma unroll
-  for (uint32_t k = 1; k < IS_SHARDS; ++k) if (r >= a.lo[k]) p = a.bits[k];
-  return p + (size_t)r * a.NWR;
-}
 
 // grid W / 256: a thread per id of the padded row
 __global__ __launch_bounds__(256) void k_is_init(IsArgs a) {
   const uint32_t j = blockIdx.x * 256 + threadIdx.x;
-  a.L[j] = ((a.ab[j >> 5] >> (j & 31u)) & 1u) ? j : KB_CENSUS_NONE;
+  a.L[j] = ((a.m.ab[j >> 5] >> (j & 31u)) & 1u) ? j : KB_CENSUS_NONE;
 }
 
 // grid W / 256: a thread per id; the 32 lanes of a half wave are one word
 __global__ __launch_bounds__(256) void k_is_words(IsArgs a) {
   const uint32_t j = blockIdx.x * 256 + threadIdx.x;
   if (j == 0) *a.changed = 0;
-  const bool on = (a.ab[j >> 5] >> (j & 31u)) & 1u;
+  const bool on = (a.m.ab[j >> 5] >> (j & 31u)) & 1u;
   uint32_t lo = 0xFFFFFFFFu, hi = 0;
   if (on) {
     const uint32_t x = a.L[j];                    // <= j < C: an id
@@ -119,12 +107,12 @@ __device__ __attribute__((always_inline)) inline bool is_push(const IsArgs& a, u
 __global__ __launch_bounds__(256) void k_is_sweep(IsArgs a) {
   const uint32_t l = lane();
   const uint32_t i = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-  if (i >= a.C) return;
-  if (!((uint32_t)__builtin_amdgcn_readfirstlane((int)a.ab[i >> 5]) >> (i & 31u) & 1u)) return;   // scalar: the row is not read
-  const uint4* row = reinterpret_cast<const uint4*>(is_row(a, i));
-  const uint4* ab4 = reinterpret_cast<const uint4*>(a.ab);
-  const uint4* vb4 = reinterpret_cast<const uint4*>(a.vb);
-  const uint32_t steps = a.NWR / IS_STEP_WORDS;
+  if (i >= a.rows.C) return;
+  if (!((uint32_t)__builtin_amdgcn_readfirstlane((int)a.m.ab[i >> 5]) >> (i & 31u) & 1u)) return;   // scalar: the row is not read
+  const uint4* row = reinterpret_cast<const uint4*>(bit_row(a.rows, i));
+  const uint4* ab4 = reinterpret_cast<const uint4*>(a.m.ab);
+  const uint4* vb4 = reinterpret_cast<const uint4*>(a.m.vb);
+  const uint32_t steps = a.rows.NWR / IS_STEP_WORDS;
   uint32_t m = a.L[i], n = 0;
   for (uint32_t s = 0; s < steps; ++s) {
     const uint32_t g = s * 64 + l;                               // this lane's 16-byte group: words 4 g .. 4 g + 3
@@ -161,23 +149,21 @@ struct IsPart {
   uint32_t sweeps = 0;
   double ms = 0;
 };
-// words of the pass's scratch: the three masks of k_cs_masks, the two word summaries, the labels, then (zeroed before
-// every pass) the rows' entry counts and the changed word.  Every part but the last two is whole KiB, so the 16-byte
-// loads of the masks and the labels are aligned.
-static size_t is_scratch_words(uint32_t W, uint32_t C) { return 5ull * (W / 32) + W + C + 1; }
+// the scratch (a.rows set): masks, labels (16-byte loads), word summaries; cleared every pass: entry counts, changed
+static void is_lay(Carve& c, kb::IsArgs& a, uint32_t W) {
+  const uint32_t C = a.rows.C, NWR = a.rows.NWR;
+  a.m = carve_masks(c, NWR, false);
+  a.L = c.take<uint32_t>(W, 16); a.wmin = c.take<uint32_t>(NWR); a.wmax = c.take<uint32_t>(NWR);
+  c.zero_from(); a.rown = c.take<uint32_t>(C); a.changed = c.take<uint32_t>(1); c.zero_to();
+}
 
-// The sweeps over the rows behind a.bits / a.lo with the running set dm.alive (dm: what k_cs_masks reads: C, NWR,
-// alive, ext), scratch at `buf`, on stream st.
-static int is_exec(uint32_t* buf, kb::IsArgs a, const Dev& dm, uint32_t W, hipStream_t st, IsPart& p) {
-  const uint32_t C = a.C, NWR = a.NWR;
-  CsDense m{};
-  m.ab = buf; m.sb = m.ab + NWR; m.vb = m.sb + NWR;
-  a.ab = m.ab; a.vb = m.vb; a.wmin = m.vb + NWR; a.wmax = a.wmin + NWR; a.L = a.wmax + NWR; a.rown = a.L + W;
-  a.changed = a.rown + C;
+// the sweeps over a.rows with the running set `alive` ([C], device), scratch laid out in `c` by is_lay, on stream st
+static int is_exec(const Carve& c, const kb::IsArgs& a, const uint8_t* alive, uint32_t W, hipStream_t st, IsPart& p) {
+  const uint32_t C = a.rows.C;
   CsTimer tm;
   if (!tm.start(st)) { seterr("islands: events"); return KB_IO_ERROR; }
-  HIPCHK(hipMemsetAsync(a.rown, 0, 4ull * ((size_t)C + 1), st));
-  k_cs_masks<<<(NWR + 255) / 256, 256, 0, st>>>(dm, m);
+  HIPCHK(hipMemsetAsync(c.zero_ptr(), 0, c.zero_bytes(), st));
+  id_masks(alive, nullptr, C, a.rows.NWR, a.m, st);
   k_is_init<<<W / 256, 256, 0, st>>>(a);
   HIPCHK(hipGetLastError());
   p.sweeps = 0;
@@ -215,30 +201,16 @@ extern "C" int kb_sim_islands(kb_sim* s, kb_islands* out, uint32_t* label, uint3
   if (!s) return KB_INVALID_ARGUMENT;
   { const int rc = census_caps("kb_sim_islands", out, any_of(label, size), cap_ids, s->C, nullptr, 0, 0); if (rc) return rc; }
   { const int rc = census_gate(s, "kb_sim_islands", IS_REFUSE); if (rc) return rc; }
-  kb_sim* h = is_group(s) ? s->shards[0] : s;     // owns the scratch and the stream; every shard is on its device
-  (void)hipSetDevice(h->device);
-  if (is_group(s)) {
-    const int rc = route(s, R_ALL, 0, [](auto* e) -> int { HIPCHK(hipStreamSynchronize(eng_stream(e))); return KB_OK; });
-    if (rc) return rc;
-  }
-  const Dev& d = h->d;
   kb::IsArgs a{};
-  a.C = s->C; a.NWR = d.NWR;
-  for (uint32_t k = 0; k < IS_SHARDS; ++k) { a.bits[k] = d.bits; a.lo[k] = 0xFFFFFFFFu; }
-  if (is_group(s)) {
-    for (size_t k = 0; k < s->shards.size() && k < IS_SHARDS; ++k) { a.bits[k] = s->shards[k]->d.bits; a.lo[k] = s->shards[k]->lo; }
-  }
-  a.lo[0] = 0;
-  {                                               // is_row's precondition: contiguous shards in row order, covering [0, C)
-    const size_t ns = is_group(s) ? s->shards.size() : 1;
-    bool ok = ns >= 1 && ns <= IS_SHARDS && (is_group(s) ? s->shards[0]->lo == 0 && s->shards[ns - 1]->hi == s->C : true);
-    for (size_t k = 1; ok && k < ns; ++k) ok = s->shards[k]->lo == s->shards[k - 1]->hi && a.lo[k] > a.lo[k - 1];
-    if (!ok) { seterr("kb_sim_islands: the group's shards are not contiguous in row order"); return KB_INVALID_OPERATION; }
-  }
+  kb_sim* h = nullptr;
+  { const int rc = bit_rows(s, "kb_sim_islands", a.rows, &h); if (rc) return rc; }
+  const Dev& d = h->d;
   if (h->W % 8192 || d.NWR != h->W / 32) { seterr("kb_sim_islands: the row stride is not a multiple of 8192 ids"); return KB_INVALID_OPERATION; }
-  if (!h->is_buf) HIPCHK(talloc(h, &h->is_buf, is_scratch_words(h->W, s->C)));
+  auto lay = [&](Carve& c) { is_lay(c, a, h->W); };
+  if (!h->is_buf) HIPCHK(talloc(h, &h->is_buf, carve_bytes(lay) / 4));
+  const Carve c = carve(h->is_buf, lay);
   IsPart p;
-  { const int rc = is_exec(h->is_buf, a, d, h->W, h->st, p); if (rc) return rc; }
+  { const int rc = is_exec(c, a, d.alive, h->W, h->st, p); if (rc) return rc; }
   s->census_ms[CM_ISLANDS] = p.ms;
   return is_finish("kb_sim_islands", p, h->round, out, label, size);
 }
@@ -253,22 +225,18 @@ extern "C" int kb_islands_of(int device, const uint32_t* bits, const uint8_t* ru
   OfScope o;
   { const int rc = o.open(device, "kb_islands_of"); if (rc) return rc; }
   const uint32_t C = (uint32_t)capacity, W = (C + 8191) / 8192 * 8192, NWR = W / 32;
-  // the scratch first (whole KiB in front of its masks and labels), then the bit table (whole KiB each row), then the
-  // running flags and as many zero bytes for the external set k_cs_masks reads
-  const size_t scr_b = 4ull * is_scratch_words(W, C), o_bits = (scr_b + 255) & ~(size_t)255, bits_b = 4ull * C * NWR,
-               o_run = o_bits + bits_b, o_ext = o_run + C;
-  { const int rc = dev_reserve(&o.buf, &o.cap, o_ext + C, "kb_islands_of: device allocation failed"); if (rc) return rc; }
-  char* b = static_cast<char*>(o.buf);
-  HIPCHK(hipMemcpyAsync(b + o_bits, bits, bits_b, hipMemcpyHostToDevice, o.st));
-  HIPCHK(hipMemcpyAsync(b + o_run, running, C, hipMemcpyHostToDevice, o.st));
-  HIPCHK(hipMemsetAsync(b + o_ext, 0, C, o.st));
-  Dev dm{};
-  dm.C = C; dm.NWR = NWR; dm.alive = reinterpret_cast<uint8_t*>(b + o_run); dm.ext = reinterpret_cast<uint8_t*>(b + o_ext);
   kb::IsArgs a{};
-  a.C = C; a.NWR = NWR;
-  for (uint32_t k = 0; k < IS_SHARDS; ++k) { a.bits[k] = reinterpret_cast<const uint32_t*>(b + o_bits); a.lo[k] = 0xFFFFFFFFu; }
-  a.lo[0] = 0;
+  uint32_t* tab = nullptr; uint8_t* run = nullptr;
+  auto lay = [&](Carve& c) {                      // the bit table (16-byte loads), the running flags, then the pass's scratch
+    tab = c.take<uint32_t>((size_t)C * NWR, 16); run = c.take<uint8_t>(C);
+    bit_rows(tab, C, NWR, a.rows);
+    is_lay(c, a, W);
+  };
+  { const int rc = dev_reserve(&o.buf, &o.cap, carve_bytes(lay), "kb_islands_of: device allocation failed"); if (rc) return rc; }
+  const Carve c = carve(o.buf, lay);
+  HIPCHK(hipMemcpyAsync(tab, bits, 4ull * C * NWR, hipMemcpyHostToDevice, o.st));
+  HIPCHK(hipMemcpyAsync(run, running, C, hipMemcpyHostToDevice, o.st));
   IsPart p;
-  { const int rc = is_exec(reinterpret_cast<uint32_t*>(b), a, dm, W, o.st, p); if (rc) return rc; }
+  { const int rc = is_exec(c, a, run, W, o.st, p); if (rc) return rc; }
   return is_finish("kb_islands_of", p, -1, out, label, size);
 }

@@ -178,22 +178,14 @@ __global__ __launch_bounds__(256) void k_lat_census(LcArgs a) {
 }  // namespace kb
 
 // ---- host side -------------------------------------------------------------------------------------------
-// the scratch of one pass: byte offsets into one allocation; [0, zero) is cleared, [mn, bytes) set to all ones
-struct LcPlan { size_t sum = 0, rsum = 0, mb = 0, mx = 0, rcnt = 0, zero = 0, mn = 0, bytes = 0; };
-static LcPlan lc_plan(uint32_t C, uint32_t RS) {
-  LcPlan p;
-  size_t o = 256;                                   // the summary words
-  p.sum = o; o += 8ull * C;
-  p.rsum = o; o += 8ull * RS;
-  p.mb = o; o += 4ull * C;
-  p.mx = o; o += 4ull * C;
-  p.rcnt = o; o += 4ull * RS;
-  p.zero = o;
-  p.mn = o; o += 4ull * C;
-  p.bytes = (o + 15) & ~(size_t)15;
-  return p;
+// the scratch of one pass (a.C, a.RS set): all but the minima is cleared before every pass, the minima set to all ones
+static void lc_lay(Carve& c, kb::LcArgs& a) {
+  c.zero_from();
+  a.head = c.take<unsigned long long>(kb::LC_HEAD); a.sum = c.take<unsigned long long>(a.C); a.rsum = c.take<unsigned long long>(a.RS);
+  a.mb = c.take<uint32_t>(a.C); a.mx = c.take<uint32_t>(a.C); a.rcnt = c.take<uint32_t>(a.RS);
+  c.zero_to();
+  a.mn = c.take<uint32_t>(a.C);
 }
-static_assert(kb::LC_HEAD * 8 <= 256, "kb_latcensus.h scratch layout");
 
 // a census being put together: the ids' and rows' arrays, added to shard by shard
 struct LcPart {
@@ -208,19 +200,14 @@ static void lc_part_init(LcPart& p, size_t n_ids, size_t n_rows) {
   p.rcnt.assign(n_rows, 0); p.rsum.assign(n_rows, 0);
 }
 
-// The pass over a.lat / a.bits / a.alive in scratch `buf` laid out by `pl`, on stream st; its results join `p`,
-// the rows' at index lo onwards.
-static int lc_exec(void* buf, const LcPlan& pl, kb::LcArgs a, hipStream_t st, uint32_t lo, bool want_rows, LcPart& p) {
-  char* b = static_cast<char*>(buf);
-  a.head = reinterpret_cast<unsigned long long*>(b);
-  a.sum = reinterpret_cast<unsigned long long*>(b + pl.sum); a.rsum = reinterpret_cast<unsigned long long*>(b + pl.rsum);
-  a.mb = reinterpret_cast<uint32_t*>(b + pl.mb); a.mx = reinterpret_cast<uint32_t*>(b + pl.mx);
-  a.rcnt = reinterpret_cast<uint32_t*>(b + pl.rcnt); a.mn = reinterpret_cast<uint32_t*>(b + pl.mn);
+// The pass over a.lat / a.bits / a.alive with the scratch laid out in `c` by lc_lay, on stream st; its results join
+// `p`, the rows' at index lo onwards.
+static int lc_exec(const Carve& c, const kb::LcArgs& a, hipStream_t st, uint32_t lo, bool want_rows, LcPart& p) {
   const uint32_t C = a.C, R = a.R;
   CsTimer tm;
   if (!tm.start(st)) { seterr("latency census: events"); return KB_IO_ERROR; }
-  HIPCHK(hipMemsetAsync(b, 0, pl.zero, st));
-  HIPCHK(hipMemsetAsync(b + pl.mn, 0xFF, 4ull * C, st));
+  HIPCHK(hipMemsetAsync(c.zero_ptr(), 0, c.zero_bytes(), st));
+  HIPCHK(hipMemsetAsync(a.mn, 0xFF, 4ull * C, st));
   k_lat_census<<<dim3((C + kb::LC_SLAB - 1) / kb::LC_SLAB, (a.RS + kb::LC_TILE_ROWS - 1) / kb::LC_TILE_ROWS), 256, 0, st>>>(a);
   tm.stop(st);
   HIPCHK(hipGetLastError());
@@ -273,13 +260,13 @@ static void lc_deliver(const LcPart& p, uint32_t* measured_by, uint64_t* sum_ms,
 static int lc_leaf(kb_sim* s, bool want_rows, LcPart& p) {
   (void)hipSetDevice(s->device);
   const Dev& d = s->d;
-  const uint32_t RS = lat_stride(s->R);
-  const LcPlan pl = lc_plan(s->C, RS);
-  if (!s->lc_buf) HIPCHK(talloc(s, &s->lc_buf, pl.bytes / 4));
   kb::LcArgs a{};
   a.lat = d.lat; a.bits = d.bits + (size_t)s->lo * d.NWR; a.alive = d.alive + s->lo;   // d.bits is biased by -lo rows
-  a.R = s->R; a.RS = RS; a.C = s->C; a.NWR = d.NWR;
-  return lc_exec(s->lc_buf, pl, a, s->st, s->lo, want_rows, p);
+  a.R = s->R; a.RS = lat_stride(s->R); a.C = s->C; a.NWR = d.NWR;
+  auto lay = [&](Carve& c) { lc_lay(c, a); };
+  if (!s->lc_buf) HIPCHK(talloc(s, &s->lc_buf, carve_bytes(lay) / 4));
+  const Carve c = carve(s->lc_buf, lay);
+  return lc_exec(c, a, s->st, s->lo, want_rows, p);
 }
 static int lc_leaf(SpSim*, bool, LcPart&) { return KB_INVALID_OPERATION; }   // not reached: census_gate refuses sparse rows
 
@@ -325,20 +312,21 @@ extern "C" int kb_latency_census_of(int device, const uint16_t* lat, const uint8
       for (size_t j = 0; j < C; ++j) if (member[i * C + j]) hb[i * NWR + (j >> 5)] |= 1u << (j & 31);
     ha.resize(R);
     for (size_t i = 0; i < R; ++i) ha[i] = running[i] != 0;
-    const LcPlan pl = lc_plan(C, RS);
-    const size_t lat_b = 2ull * C * RS, bits_b = 4ull * R * NWR, o_bits = (lat_b + 255) & ~(size_t)255,
-                 o_alive = o_bits + bits_b, o_scr = (o_alive + R + 255) & ~(size_t)255;
-    { const int rc = dev_reserve(&o.buf, &o.cap, o_scr + pl.bytes, "kb_latency_census_of: device allocation failed"); if (rc) return rc; }
-    char* buf = static_cast<char*>(o.buf);
-    HIPCHK(hipMemsetAsync(buf, 0xFF, lat_b, o.st));                                    // the padding rows: None
-    HIPCHK(hipMemcpy2DAsync(buf, 2ull * RS, lat, 2ull * R, 2ull * R, C, hipMemcpyHostToDevice, o.st));
-    HIPCHK(hipMemcpyAsync(buf + o_bits, hb.data(), bits_b, hipMemcpyHostToDevice, o.st));
-    HIPCHK(hipMemcpyAsync(buf + o_alive, ha.data(), R, hipMemcpyHostToDevice, o.st));
     kb::LcArgs a{};
-    a.lat = reinterpret_cast<const uint16_t*>(buf); a.bits = reinterpret_cast<const uint32_t*>(buf + o_bits);
-    a.alive = reinterpret_cast<const uint8_t*>(buf + o_alive);
     a.R = R; a.RS = RS; a.C = C; a.NWR = NWR;
-    { const int rc = lc_exec(buf + o_scr, pl, a, o.st, 0, measured || row_sum_ms, p); if (rc) return rc; }
+    uint16_t* dl = nullptr; uint32_t* db = nullptr; uint8_t* da = nullptr;
+    auto lay = [&](Carve& c) {                      // the table and the bit rows (16-byte loads), the flags, the scratch
+      dl = c.take<uint16_t>((size_t)C * RS, 16); db = c.take<uint32_t>((size_t)R * NWR, 16); da = c.take<uint8_t>(R);
+      lc_lay(c, a);
+    };
+    { const int rc = dev_reserve(&o.buf, &o.cap, carve_bytes(lay), "kb_latency_census_of: device allocation failed"); if (rc) return rc; }
+    const Carve c = carve(o.buf, lay);
+    a.lat = dl; a.bits = db; a.alive = da;
+    HIPCHK(hipMemsetAsync(dl, 0xFF, 2ull * C * RS, o.st));                             // the padding rows: None
+    HIPCHK(hipMemcpy2DAsync(dl, 2ull * RS, lat, 2ull * R, 2ull * R, C, hipMemcpyHostToDevice, o.st));
+    HIPCHK(hipMemcpyAsync(db, hb.data(), 4ull * R * NWR, hipMemcpyHostToDevice, o.st));
+    HIPCHK(hipMemcpyAsync(da, ha.data(), R, hipMemcpyHostToDevice, o.st));
+    { const int rc = lc_exec(c, a, o.st, 0, measured || row_sum_ms, p); if (rc) return rc; }
   }
   lc_summary(p, -1, out);
   lc_deliver(p, measured_by, sum_ms, min_ms, max_ms, measured, row_sum_ms);

@@ -29,35 +29,24 @@ constexpr uint32_t RC_T = RC_B / 64;              // 64-id tiles per block side 
 constexpr uint32_t RC_LD = RC_T + 1;              // u64 per staged row: 72-byte rows, so the 32 lanes of a
                                                   // ds_read_b64 half fall on 32 distinct bank pairs
 constexpr uint32_t RC_THREADS = 64 * RC_T;
-constexpr uint32_t RC_SHARDS = 8;                 // XMAX
 
 struct RcArgs {
-  const uint32_t* bits[RC_SHARDS];                // every shard's member bits (biased: indexed by global row)
-  uint32_t lo[RC_SHARDS];                         // its first row; 0xFFFFFFFF for unused entries
-  uint32_t C, NWR, nb;                            // capacity, words per row, blocks per side
-  const uint32_t* ab;                             // [W/32] running ids (k_cs_masks)
+  BitRows rows;                                   // the member bits of rows.C ids (kb_bitpass.h)
+  uint32_t nb;                                    // blocks per side
+  const uint32_t* ab;                             // [W/32] running ids (k_id_masks)
   uint32_t* cnt;                                  // [3][C] mutual, lacks, lacked_by (zeroed)
   uint32_t* flag;                                 // [nb][nb] block pair (I, J) holds a mutual gap (zeroed)
   uint2* pairs; unsigned long long* npairs;       // the pair pass: its buffer, entries appended (zeroed)
   unsigned long long cap;                         // entries the buffer holds
 };
 
-// The shard that holds row r: the last entry whose first row is <= r.  This needs lo[] ascending with lo[0] = 0 and
-// the unused entries at 0xFFFFFFFF; kb_sim_reciprocity checks that before it launches.
-__device__ __attribute__((always_inline)) inline const uint32_t* rc_row(const RcArgs& a, uint32_t r) {
-  const uint32_t* p = a.bits[0];
-#pragma unroll
-  for (uint32_t k = 1; k < RC_SHARDS; ++k) if (r >= a.lo[k]) p = a.bits[k];
-  return p + (size_t)r * a.NWR;
-}
-
 // the running rows' 64-byte segments of rows [rb*512, +512) x columns [cb*512, +512): a thread's four loads
 __device__ __attribute__((always_inline)) inline void rc_load(const RcArgs& a, uint32_t rb, uint32_t cb, uint4 (&v)[4]) {
 #pragma unroll
   for (uint32_t p = 0; p < 4; ++p) {
     const uint32_t row = rb * RC_B + p * 128 + (threadIdx.x >> 2);
-    const bool on = row < a.C && ((a.ab[row >> 5] >> (row & 31u)) & 1u);
-    v[p] = on ? *reinterpret_cast<const uint4*>(rc_row(a, row) + cb * (RC_B / 32) + (threadIdx.x & 3u) * 4)
+    const bool on = row < a.rows.C && ((a.ab[row >> 5] >> (row & 31u)) & 1u);
+    v[p] = on ? *reinterpret_cast<const uint4*>(bit_row(a.rows, row) + cb * (RC_B / 32) + (threadIdx.x & 3u) * 4)
               : uint4{0, 0, 0, 0};
   }
 }
@@ -143,20 +132,20 @@ __global__ __launch_bounds__(RC_THREADS) void k_rc_count(RcArgs a) {
     }
   }
   const uint32_t i = BI * RC_B + ti * 64 + l;
-  if (i < a.C) {
+  if (i < a.rows.C) {
     if (nm) atomicAdd(&a.cnt[i], nm);
-    if (nl) atomicAdd(&a.cnt[(size_t)a.C + i], nl);
-    if (nh) atomicAdd(&a.cnt[2 * (size_t)a.C + i], nh);
+    if (nl) atomicAdd(&a.cnt[(size_t)a.rows.C + i], nl);
+    if (nh) atomicAdd(&a.cnt[2 * (size_t)a.rows.C + i], nh);
   }
   if (__ballot(any) && l == 0) a.flag[(size_t)BI * a.nb + BJ] = 1;
   if (diag) return;                               // workgroup-uniform
   __syncthreads();
   const uint32_t j = BJ * RC_B + threadIdx.x;
-  if (j < a.C) {
+  if (j < a.rows.C) {
 #pragma unroll
     for (uint32_t q = 0; q < 3; ++q) {
       const uint32_t n = cj[q * RC_B + threadIdx.x];
-      if (n) atomicAdd(&a.cnt[q * (size_t)a.C + j], n);
+      if (n) atomicAdd(&a.cnt[q * (size_t)a.rows.C + j], n);
     }
   }
 }
@@ -210,38 +199,24 @@ extern "C" int kb_sim_reciprocity(kb_sim* s, kb_reciprocity* out, uint32_t* mutu
   { const int rc = census_gate(s, "kb_sim_reciprocity", {"; the census needs every rank's", "need an O(entries) algorithm of their own (not built yet)", nullptr});
     if (rc) return rc; }
   { const int rc = census_caps("kb_sim_reciprocity", out, nullptr, 0, 0, any_of(mutual, lacks, lacked_by), cap_rows, s->C); if (rc) return rc; }
-  kb_sim* h = is_group(s) ? s->shards[0] : s;     // owns the scratch and the stream; every shard is on its device
-  (void)hipSetDevice(h->device);
-  if (is_group(s)) {
-    const int rc = route(s, R_ALL, 0, [](auto* e) -> int { HIPCHK(hipStreamSynchronize(eng_stream(e))); return KB_OK; });
-    if (rc) return rc;
-  }
+  RcArgs a{};
+  kb_sim* h = nullptr;
+  { const int rc = bit_rows(s, "kb_sim_reciprocity", a.rows, &h); if (rc) return rc; }
   const Dev& d = h->d;
   const uint32_t C = s->C, nb = (C + RC_B - 1) / RC_B;
-  // scratch: the three masks of k_cs_masks, then (zeroed each call) the pair counter, the counts, the flags
-  const size_t zero_words = 2 + 3ull * C + (size_t)nb * nb;
-  if (!h->rc_buf) HIPCHK(talloc(h, &h->rc_buf, 3ull * d.NWR + zero_words));
-  CsDense m{};
-  m.ab = h->rc_buf; m.sb = m.ab + d.NWR; m.vb = m.sb + d.NWR;
-  RcArgs a{};
-  a.npairs = reinterpret_cast<unsigned long long*>(m.vb + d.NWR);   // 3 * NWR words in: 8-byte aligned
-  a.cnt = m.vb + d.NWR + 2; a.flag = a.cnt + 3ull * C;
-  a.ab = m.ab; a.C = C; a.NWR = d.NWR; a.nb = nb;
-  for (uint32_t k = 0; k < RC_SHARDS; ++k) { a.bits[k] = d.bits; a.lo[k] = 0xFFFFFFFFu; }
-  if (is_group(s)) {
-    for (size_t k = 0; k < s->shards.size() && k < RC_SHARDS; ++k) { a.bits[k] = s->shards[k]->d.bits; a.lo[k] = s->shards[k]->lo; }
-  }
-  a.lo[0] = 0;
-  {                                               // rc_row's precondition: contiguous shards in row order, covering [0, C)
-    const size_t ns = is_group(s) ? s->shards.size() : 1;
-    bool ok = ns >= 1 && ns <= RC_SHARDS && (is_group(s) ? s->shards[0]->lo == 0 && s->shards[ns - 1]->hi == C : true);
-    for (size_t k = 1; ok && k < ns; ++k) ok = s->shards[k]->lo == s->shards[k - 1]->hi && a.lo[k] > a.lo[k - 1];
-    if (!ok) { seterr("kb_sim_reciprocity: the group's shards are not contiguous in row order"); return KB_INVALID_OPERATION; }
-  }
+  a.nb = nb;
+  IdMasks m{};
+  auto lay = [&](Carve& c) {                      // the masks (8-byte loads of ab), then, cleared every call, the pair
+    m = carve_masks(c, d.NWR, false);             // counter, the counts and the flags
+    c.zero_from(); a.npairs = c.take<unsigned long long>(1); a.cnt = c.take<uint32_t>(3ull * C); a.flag = c.take<uint32_t>((size_t)nb * nb); c.zero_to();
+  };
+  if (!h->rc_buf) HIPCHK(talloc(h, &h->rc_buf, carve_bytes(lay) / 4));
+  const Carve c = carve(h->rc_buf, lay);
+  a.ab = m.ab;
   CsTimer tm;
   if (!tm.start(h->st)) { seterr("reciprocity: events"); return KB_IO_ERROR; }
-  HIPCHK(hipMemsetAsync(a.npairs, 0, 4ull * zero_words, h->st));
-  k_cs_masks<<<(d.NWR + 255) / 256, 256, 0, h->st>>>(d, m);
+  HIPCHK(hipMemsetAsync(c.zero_ptr(), 0, c.zero_bytes(), h->st));
+  id_masks(d.alive, nullptr, C, d.NWR, m, h->st);
   k_rc_count<<<dim3(nb, nb), RC_THREADS, 0, h->st>>>(a);
   tm.stop(h->st);
   HIPCHK(hipGetLastError());

@@ -2219,6 +2219,7 @@ extern "C" int kb_sim_debug_fold(kb_sim* s, const kb_fold_probe* p) {
 
 // ---- the censuses' shared host frame ------------------------------------------------------------------------
 #include "kb_censusframe.h"
+#include "kb_bitpass.h"
 
 // ---- the view census (include/kaboodle_census.h) ----------------------------------------------------------
 #include "kb_census.h"

@@ -1,6 +1,7 @@
 """The island census on the GPU (kb_sim_islands, include/kaboodle_islands.h; kernels in
 kaboodle_amd/csrc/kb_islands.h): crafted graphs through kb_islands_of against islands_ref, meshes against the CPU
-oracle through the same call every round (unsharded and as 3 shards), read-only, and the refusals."""
+oracle through the same call every round (unsharded and as 3 shards; 8 shards against the unsharded handle), read-only,
+and the refusals."""
 from __future__ import annotations
 
 import ctypes as C
@@ -229,6 +230,23 @@ def test_islands_equal_oracle_every_round(gpu, name, shards):
         assert any(w.summary["rebroadcasting"] > 3 for w in want)
 
 
+def test_islands_eight_shards_equal_the_unsharded_handle(gpu):
+    """The row table at its last entry: 8 shards of 4 rows (split32, the smallest case here that 8 shards can split)
+    against the unsharded handle, summary and arrays, every round."""
+    has_kernel(gpu)
+    case, rounds = CASES["split32"]
+    assert min(c["cfg"].capacity for c, _ in CASES.values() if 7 * -(-c["cfg"].capacity // 8) < c["cfg"].capacity) == 32
+    with Sim(gpu, case["cfg"]) as one, Sim(gpu, case["cfg"], shards=8) as grp:
+        for g in (one, grp):
+            parity.setup(g, case)
+        for r in range(rounds):
+            parity.apply_events((one, grp), case, r)
+            one.step(1)
+            grp.step(1)
+            d = grp.islands().same_as(one.islands())
+            assert not d, f"round {r}: " + "; ".join(d[:6])
+
+
 def test_islands_exact_lru(gpu):
     case, rounds = SPLIT
     run_against(gpu, "lru:split32", parity.with_cfg(case, variant=KB_VARIANT_EXACT_LRU), rounds)
@@ -236,7 +254,7 @@ def test_islands_exact_lru(gpu):
 
 # ---- the handle's contract -----------------------------------------------------------------------------------------
 def test_islands_is_read_only(gpu):
-    """Two meshes side by side, one taking the island census (and the view census, whose k_cs_masks it shares) every
+    """Two meshes side by side, one taking the island census (and the view census, whose k_id_masks it shares) every
     round: the complete state and the view census's results stay identical."""
     has_kernel(gpu)
     case, rounds = STD["churn_loss_512"]

@@ -98,6 +98,23 @@ def test_reciprocity_three_shards(gpu):
     run_against(gpu, "std:churn_loss_512", case, rounds, shards=3)
 
 
+def test_reciprocity_eight_shards_equal_the_unsharded_handle(gpu):
+    """The row table at its last entry: 8 shards of 8 rows (fresh_ids, the smallest case here that 8 shards can split)
+    against the unsharded handle, summary, arrays and pair list, every round."""
+    has_kernel(gpu)
+    case, rounds = CASES["fresh_ids"]
+    assert min(c["cfg"].capacity for c, _ in CASES.values() if 7 * -(-c["cfg"].capacity // 8) < c["cfg"].capacity) == 64
+    with Sim(gpu, case["cfg"]) as one, Sim(gpu, case["cfg"], shards=8) as grp:
+        for g in (one, grp):
+            parity.setup(g, case)
+        for r in range(rounds):
+            parity.apply_events((one, grp), case, r)
+            one.step(1)
+            grp.step(1)
+            d = grp.reciprocity().same_as(one.reciprocity())
+            assert not d, f"round {r}: " + "; ".join(d[:6])
+
+
 def test_counts_past_32_bits_closed_form(gpu):
     """The one full-size case: after the first round of a join start nobody knows anybody, so every pair of the
     66,000 observers is a mutual gap; their number is above 2^31 and every row's count above 2^16."""
