@@ -126,8 +126,11 @@ enum {
                                 per lane) at any width                                                 */
   KB_DBG_A3X_WIDE = 512u,    /* KB_VARIANT_EXACT_LRU: A3 by the one-pass kernel of rows above 512K ids at any
                                 width (wins over KB_DBG_A3X_KPL8)                                      */
-  KB_DBG_WAVE0_SERIAL = 1024u /* wave 0 of a round with joiners keeps the one KnownPeers launch before the
+  KB_DBG_WAVE0_SERIAL = 1024u,/* wave 0 of a round with joiners keeps the one KnownPeers launch before the
                                 in-order handlers instead of the BIG groups on the side stream
+                                (A/B and parity surface)                               */
+  KB_DBG_RESP_SERIAL = 2048u /* the Join responses all run before the tick, in one phase, instead of split around
+                                A2 with most of them beside the tick on a third stream
                                 (A/B and parity surface)                               */
 };
 

@@ -22,6 +22,7 @@ KB_DBG_NO_UNION = 128            # row shards: Join responses as id lists, not o
 KB_DBG_A3X_KPL8 = 256            # exact A3 order by the kernel of 128K-512K-id rows, at any width
 KB_DBG_A3X_WIDE = 512            # exact A3 order by the one-pass kernel of rows above 512K ids, at any width
 KB_DBG_WAVE0_SERIAL = 1024       # wave 0 with joiners: one KnownPeers launch, no BIG groups on the side stream
+KB_DBG_RESP_SERIAL = 2048        # Join responses all before the tick, in one phase, none beside it on the third stream
 KB_VARIANT_SAME_WINDOW_BCAST, KB_VARIANT_EXACT_LRU = 1, 2  # the first oracle-only; the second on the GPU too (bench default)
 KB_STAT_NO_SF_FAILED_DROPS = 1
 KB_VARIANT_SPARSE_ROWS = 4       # the configs[4] layout: oracle and the HIP library (unsharded or row shards)

@@ -42,7 +42,8 @@ enum CtrIdx {
   C_ROUND,                        // the round being simulated (k_log_mark): graph-replayed kernels read it here
   C_PATHS,                        // OR of the PATH_* bits of the kernel variants that did work (test surface)
   C_DBG_SLOW_LONG, C_DBG_SLOW_NONMEM, C_DBG_SLOW_DIRTY, C_DBG_SLOW_KPR, C_DBG_SLOW_OTHER,   // KB_DEV & 256: why k_proc
-  C_RESTN,                        // responders k_resp_wave left to k_resp_node (their list: the wave lists' slow buffer)
+  C_RESTN,                        // responders k_resp_wave left to k_resp_node, phases 0 and 1 (their list: rest[0]; phase 2,
+                                  // beside the tick, has a list and a counter of its own: rest[1], rest2n)
   C_XREC, C_XPAY,                 // exported records / KnownPeers ids this round (external peers)
   NCTR
 };
@@ -55,7 +56,10 @@ enum : uint32_t { PATH_PHASEB_HBM = 1, PATH_RESP_SCRATCH_SAMPLED = 2, PATH_RESP_
                   PATH_ROWPASS_LDS_HBM_LISTS = 1024,   // row pass k_rowpass<true,false>: rows staged, lists from HBM (host-set)
                   PATH_KPR_WRAPPED = 2048,             // a KPR reply proven oversize from a wrapped log ring
                   PATH_RESP_JOINERS_HBM = 4096,        // k_resp_node served a receiver with nnew > RESP_JCAP
-                  PATH_JOIN_LIST_PAST_UCAP = 8192 };   // row shards: a Join response to a joiner past UCAP crossed as a list
+                  PATH_JOIN_LIST_PAST_UCAP = 8192,     // row shards: a Join response to a joiner past UCAP crossed as a list
+                  // Join responses beside the tick
+                  PATH_RESP_PHASE1 = 16384,            // phase 1 served a responder A2 may touch, ahead of k_tick_pre
+                  PATH_A2_RESPONDER = 32768 };         // k_tick_pre removed a member from the row of one of the round's responders
 constexpr int NSEG = 64;          // fingerprint checkpoints per row
 constexpr int ZT = 9;             // LDS nibble tables for Z^0..Z^8
 constexpr int ZB = 9 * 1024;      // byte tables for Z^0..Z^8 (4 lookups per multiply)

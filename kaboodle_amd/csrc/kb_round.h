@@ -1314,11 +1314,20 @@ __device__ inline bool resp_by_wave(const Dev& d, uint32_t i, uint32_t nnew, boo
 }
 // Rows too wide for a wave's LDS copy (SG: above ≈ 110K ids; configs[3]'s 1M-id rows) keep only the head
 // (block prefix, joiners, suffix minima) in LDS and read the selects' 32-byte blocks from the row's bitset
-// itself: nothing writes a row while the Join responses are built, and a responder's row stays in L2 across
+// itself: nothing writes a responder's row while its responses are built (phases, below), and the row stays in L2 across
 // its responses.  (The workgroup path instead copied each row to HBM scratch first.)
+//
+// Phases: 0 serves every responder; 1 only those k_tick_scan flagged (a2flag: A2 may write their
+// row this round), ahead of k_tick_pre; 2 the others, beside the tick.  A wave reads the ids and flags of its next 64
+// responders in one step, a lane each, so a responder of the other phase costs its byte and nothing else.  Each phase
+// appends what it leaves to k_resp_node to a list and a counter of its own (rest, restn).
+__device__ inline bool resp_phase_serves(uint32_t phase, const uint8_t* a2flag, uint32_t i) {
+  return phase == 0 || (a2flag[i] != 0) == (phase == 1);
+}
 template <bool SG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_resp_wave(Dev d, PhaseB pb, const uint32_t* nodes, const uint32_t* nnodes_p,
-                                                   OutBuf ob, int32_t r, uint32_t* rest) {
+                                                   OutBuf ob, int32_t r, uint32_t* rest, uint32_t* restn, uint32_t phase,
+                                                   const uint8_t* a2flag) {
   extern __shared__ __attribute__((aligned(16))) uint32_t rw_lds[];
   const uint32_t NW = d.NWR, NB = d.W / 256;
   const uint32_t wv = threadIdx.x >> 6, l = lane(), nwv = blockDim.x >> 6;
@@ -1334,16 +1343,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
   const uint32_t js0 = small_lists && l < pb.nj ? pb.bjoin[l].sender : 0u;
   const uint32_t js1 = small_lists && l + 64 < pb.nj ? pb.bjoin[l + 64].sender : 0u;
   const uint32_t stride = gridDim.x * nwv;
-  uint32_t it = blockIdx.x * nwv + wv;
-  uint32_t inext = it < nnodes ? nodes[it] : 0u;
-  for (; it < nnodes; it += stride) {
-    const uint32_t i = inext;
+  for (uint32_t it0 = blockIdx.x * nwv + wv; it0 < nnodes; it0 += 64 * stride) {
+   // lane l: this wave's l-th responder from it0 on (nnodes and 64 * stride are far below 2^31)
+   const uint32_t itl = it0 + l * stride;
+   const uint32_t node_l = itl < nnodes ? nodes[itl] : 0u;
+   unsigned long long todo = __ballot(itl < nnodes && resp_phase_serves(phase, a2flag, node_l));
+   while (todo) {
+    const int tb = __ffsll((long long)todo) - 1;
+    todo &= todo - 1;
+    const uint32_t i = rdl(node_l, tb);
     const unsigned long long* nm = pb.newmask + (size_t)i * pb.JW;
     const unsigned long long* rm = pb.respmask + (size_t)i * pb.JW;
     const unsigned long long nmv = small_lists && l < pb.JW ? nm[l] : 0ull;
     const unsigned long long rmv = small_lists && l < pb.JW ? rm[l] : 0ull;
     const uint32_t n_i = d.n[i], nbase_i = pb.nbase[i], poff_i = ob.poff[i], ooff_i = ob.off[i];
-    inext = it + stride < nnodes ? nodes[it + stride] : 0u;
     const uint32_t* B = bits_of(d, i);                      // row membership after the Join group
     const uint4* B4 = reinterpret_cast<const uint4*>(B);
     // the row into LDS, every load in flight, before the wave-path test: it fails for a few responders at
@@ -1355,12 +1368,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     if (small_lists) nnew = wave_sum((uint32_t)__popcll(nmv));
     else for (uint32_t wj = 0; wj < pb.JW; ++wj) nnew += __popcll(nm[wj]);
     if (!(d.uniform && nnew <= RW_JCAP && n_i - nnew > d.capj)) {   // resp_by_wave: k_resp_node serves it
-      if (l == 0) rest[atomicAdd(&d.ctr[C_RESTN], 1u)] = i;
+      if (l == 0) rest[atomicAdd(restn, 1u)] = i;
       wait_lds();
       __builtin_amdgcn_wave_barrier();
       continue;
     }
     if (l == 0) path_hit(d, SG ? PATH_RESP_WAVE_HBM : PATH_RESP_WAVE);
+    if (l == 0 && phase == 1) path_hit(d, PATH_RESP_PHASE1);   // (one bit a call: path_hit skips when any bit of its mask is set)
     uint64_t tp0 = tdbg ? wall_clock64() : 0, tp1 = 0, tp2 = 0;
     if (small_lists) {                                      // new joiners in list order: entries l and l + 64
       const unsigned long long w0 = ((unsigned long long)rdl((uint32_t)(nmv >> 32), 0) << 32) | rdl((uint32_t)nmv, 0);
@@ -1453,11 +1467,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     }
     wait_lds();                                           // the LDS slice is reused by the next responder
     __builtin_amdgcn_wave_barrier();
+   }
   }
 }
 
 __global__ __launch_bounds__(256) void k_resp_node(Dev d, PhaseB pb, const uint32_t* nodes, const uint32_t* nnodes_p,
-                                                   OutBuf ob, int32_t r, uint32_t* gscratch, bool wave_on) {
+                                                   OutBuf ob, int32_t r, uint32_t* gscratch, bool wave_on, uint32_t phase,
+                                                   const uint8_t* a2flag) {
   extern __shared__ uint32_t lds_dyn[];
   const uint32_t NW = d.NWR, NB = d.W / 256;
   // rows wider than RESP_LDS_W keep their bitsets in a per-workgroup slice of global scratch
@@ -1473,6 +1489,9 @@ __global__ __launch_bounds__(256) void k_resp_node(Dev d, PhaseB pb, const uint3
   const uint32_t nnodes = *nnodes_p;
   for (uint32_t it = blockIdx.x; it < nnodes; it += gridDim.x) {
     const uint32_t i = nodes[it];
+    // uniform: the other phase's responder.  (Only a split round without the wave path would meet one: a list
+    // k_resp_wave left is its own phase's already, and phase 0 serves everyone)
+    if (!resp_phase_serves(phase, a2flag, i)) continue;
     const unsigned long long* nm = pb.newmask + (size_t)i * pb.JW;
     const unsigned long long* rm = pb.respmask + (size_t)i * pb.JW;
     uint32_t nnew = 0;
@@ -1567,6 +1586,7 @@ __global__ __launch_bounds__(256) void k_resp_node(Dev d, PhaseB pb, const uint3
           ob.msgs[ob.off[i] + q] = m;
           if (nk != expect) set_err(d, DERR_RESP);
           if (gscratch) path_hit(d, sample ? PATH_RESP_SCRATCH_SAMPLED : PATH_RESP_SCRATCH_FULL);
+          if (phase == 1) path_hit(d, PATH_RESP_PHASE1);
           if (!jl) path_hit(d, PATH_RESP_JOINERS_HBM);
         }
         poff += cap; q++;

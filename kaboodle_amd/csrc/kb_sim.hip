@@ -151,10 +151,10 @@ __global__ void k_build_htab(Dev d) {
 // (also hands the wave-0 scan totals to the host: tot[0..4] -> host-mapped hpin[0..4], then the
 // sequence number the host polls for)
 __global__ void k_set_cap(Dev d, const uint32_t* nresp, uint32_t* cap, uint32_t* cnt, const uint32_t* tot, uint32_t* hpin,
-                          uint32_t seq) {
+                          uint32_t seq, uint32_t* rest2n) {
   const uint32_t i = d.lo + blockIdx.x * blockDim.x + threadIdx.x;
   if (i < d.hi) { cap[i] = nresp[i] + TICK_MAX; cnt[i] = nresp[i]; }
-  if (blockIdx.x == 0 && threadIdx.x == 0) { d.ctr[C_RESTN] = 0; pin_publish(hpin, tot, 5, seq); }
+  if (blockIdx.x == 0 && threadIdx.x == 0) { d.ctr[C_RESTN] = 0; *rest2n = 0; pin_publish(hpin, tot, 5, seq); }
 }
 // device values -> the host's mapped pinned buffer, then the sequence number it polls for (sharded
 // hand-offs of all-gathered counts)
@@ -346,7 +346,9 @@ struct kb_sim {
   // side stream: kernels off the round's critical path (the running set's fingerprint, the latency sweep)
   // run beside it, forked from and joined back into st by events
   hipStream_t st2 = nullptr;
-  hipEvent_t ev_fork[4] = {nullptr, nullptr, nullptr, nullptr}, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};   // side work 0-3
+  // third stream: the Join responses of the responders A2 cannot touch, beside the tick (side work 4)
+  hipStream_t st3 = nullptr;
+  hipEvent_t ev_fork[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, ev_join[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // side work 0-4
   uint32_t C, W, S;                    // capacity, row stride, row-sweep column splits
   // row shard: this handle holds rows [lo, hi) of the mesh, R = hi - lo
   uint32_t lo, hi, R;
@@ -390,7 +392,10 @@ struct kb_sim {
   unsigned long long* newmask_base; unsigned long long* respmask_base;
   uint32_t* nresp; uint32_t* paysum; uint32_t* nbase; uint32_t* resp_off;
   uint32_t* resp_nodes; uint32_t* bf_gid; uint8_t* bf_dep;
-  uint32_t* slow;                      // the nodes of a wave k_proc_fast leaves to k_proc
+  uint32_t* slow;                      // the nodes of a wave k_proc_fast leaves to k_proc; in the tick, A2's node list
+  uint32_t* rest[2] = {nullptr, nullptr};   // the responders k_resp_wave leaves to k_resp_node: phases 0 and 1, phase 2
+  uint32_t* rest2n = nullptr;          // phase 2's list counter (phases 0 and 1: d.ctr[C_RESTN])
+  uint8_t* a2flag = nullptr;           // [R] k_tick_scan: 1 for the nodes it listed for A2
   uint32_t* defer = nullptr;           // split wave 0: the BIG KnownPeers groups' destinations, handled after the join
   uint32_t* w0ctr = nullptr;           // its counters (W0_*: deferred nodes, k_proc's tickets)
   uint16_t* lat_col;                   // [C] one node's latencies (peer_states), track_latency only
@@ -503,8 +508,9 @@ static void klaunch(kb_sim* s, int kid, F kern, dim3 grid, dim3 block, uint32_t 
   klaunch_on(s, s->st, kid, kern, grid, block, lds, args...);
 }
 // fork side work k onto st2 after everything st has queued so far / join it back into st
-static void side_fork(kb_sim* s, int k) { (void)hipEventRecord(s->ev_fork[k], s->st); (void)hipStreamWaitEvent(s->st2, s->ev_fork[k], 0); }
-static void side_done(kb_sim* s, int k) { (void)hipEventRecord(s->ev_join[k], s->st2); }
+static hipStream_t side_stream(kb_sim* s, int k) { return k == 4 ? s->st3 : s->st2; }   // side work 4 has the third stream
+static void side_fork(kb_sim* s, int k) { (void)hipEventRecord(s->ev_fork[k], s->st); (void)hipStreamWaitEvent(side_stream(s, k), s->ev_fork[k], 0); }
+static void side_done(kb_sim* s, int k) { (void)hipEventRecord(s->ev_join[k], side_stream(s, k)); }
 static void side_join(kb_sim* s, int k) { (void)hipStreamWaitEvent(s->st, s->ev_join[k], 0); }
 // fold the first n records (complete: their round has ended) into the per-kernel sums
 static void prof_resolve(kb_sim* s, size_t n) {
@@ -634,7 +640,8 @@ static void destroy_shard(kb_sim* s) {
   if (s->wave_graph) (void)hipGraphDestroy(s->wave_graph);
   if (s->st) (void)hipStreamDestroy(s->st);
   if (s->st2) (void)hipStreamDestroy(s->st2);
-  for (int k = 0; k < 4; ++k) {
+  if (s->st3) (void)hipStreamDestroy(s->st3);
+  for (int k = 0; k < 5; ++k) {
     if (s->ev_fork[k]) (void)hipEventDestroy(s->ev_fork[k]);
     if (s->ev_join[k]) (void)hipEventDestroy(s->ev_join[k]);
   }
@@ -734,6 +741,7 @@ constexpr uint32_t KB_FOLD_WAVES = 16384;                            // fold wav
   A(s->scan_tot, 32); A(s->rr, 4); A(s->scan_tiles, 5 * ((std::max<size_t>(C, (size_t)world * R) + 1023) / 1024) + 5);
   AR(s->nresp, 1); AR(s->paysum, 1); AR(s->nbase, 1); AR(s->resp_off, 1);
   A(s->resp_nodes, R); A(s->bf_gid, (size_t)C * SLOTS); A(s->bf_dep, (size_t)C * SLOTS); A(s->slow, R); A(s->defer, R); A(s->w0ctr, W0_WORDS);
+  A(s->rest[0], R); A(s->rest[1], R); A(s->rest2n, 1); AR(s->a2flag, 1);
   AR(s->ro.part, 10);
   if (xf) {
     XState& x = s->xs;
@@ -762,7 +770,8 @@ constexpr uint32_t KB_FOLD_WAVES = 16384;                            // fold wav
   s->wc.msg_cap = s->msg_cap; s->wc.pay_cap = s->pay_cap;
   if (hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess) { destroy_shard(s); seterr("stream"); return KB_IO_ERROR; }
   if (hipStreamCreateWithFlags(&s->st2, hipStreamNonBlocking) != hipSuccess) { destroy_shard(s); seterr("stream"); return KB_IO_ERROR; }
-  for (int k = 0; k < 4; ++k)
+  if (hipStreamCreateWithFlags(&s->st3, hipStreamNonBlocking) != hipSuccess) { destroy_shard(s); seterr("stream"); return KB_IO_ERROR; }
+  for (int k = 0; k < 5; ++k)
     if (hipEventCreateWithFlags(&s->ev_fork[k], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&s->ev_join[k], hipEventDisableTiming) != hipSuccess) { destroy_shard(s); seterr("events"); return KB_IO_ERROR; }
   if (hipHostMalloc((void**)&s->h_pin, 4 * PIN_WORDS, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
@@ -1249,6 +1258,8 @@ struct Round {
   uint32_t ninj = 0; bool inj_pay = false;           // records injected by external peers; they carry payload ids
   hipEvent_t er[2] = {nullptr, nullptr};             // the whole round, read back next round
   size_t krec0 = 0;                                  // profile records of earlier rounds (complete)
+  bool tick_scanned = false;                         // A1 ran ahead of the Join responses
+  bool resp_side = false;                            // phase 2 of the Join responses is on the third stream (side work 4)
 };
 constexpr uint32_t TB = 256;                         // threads of the per-node launches
 static uint32_t gnode(const kb_sim* s) { return (s->R + TB - 1) / TB; }
@@ -1394,16 +1405,25 @@ static int round_broadcasts(kb_sim* s, Round& q) {
 // The round's Join responses into the wave-0 outbox: a wave per responder where its LDS slice fits (4 responders
 // per 64 KB workgroup); wider rows keep only the slice's head in LDS and select from the row itself (up to 4 waves
 // per workgroup, as the head fits: 3 at 1M-id rows); else (or forced) a workgroup with HBM scratch
-static int launch_join_responses(kb_sim* s, Round& q, uint32_t resp_nodes) {
+//
+// phase 0: every responder, on st (the serial order).  With the overlap on (resp_overlap_on) the round instead runs
+// phase 1 on st ahead of A2 — the responders k_tick_scan flagged, a few hundred at most, on a grid of one workgroup
+// per CU — and phase 2, all the others, on the third stream beside the tick.
+static bool resp_rows_hbm(const kb_sim* s) { return s->W > RESP_LDS_W || (s->d.dbg & KB_DBG_RESP_HBM); }
+static int launch_join_responses(kb_sim* s, Round& q, uint32_t resp_nodes, uint32_t phase) {
   Dev& d = s->d;
   const int32_t r = q.r;
   OutBuf& o0 = s->ob[0];
+  hipStream_t st = phase == 2 ? s->st3 : s->st;
+  uint32_t* rest = s->rest[phase == 2];
+  uint32_t* restn = phase == 2 ? s->rest2n : d.ctr + C_RESTN;
+  const uint32_t wcap = phase == 1 ? s->ncu : 4096;            // workgroups of the wave path
   const uint32_t grid = std::min<uint32_t>(resp_nodes, 4096);   // (the workgroup path: 2 per CU when it serves only
                                                                // the few responders the wave path lists)
   const size_t words = resp_words(d.NWR, s->W / 256);
   uint32_t* scratch = nullptr;
   size_t lds = 4 * words;
-  const bool resp_hbm = s->W > RESP_LDS_W || (d.dbg & KB_DBG_RESP_HBM);
+  const bool resp_hbm = resp_rows_hbm(s);
   if (resp_hbm) {
     { const int rc = eng_grow(s, &s->resp_scratch, &s->resp_scratch_words, words * grid); if (rc) return rc; }
     scratch = s->resp_scratch;
@@ -1417,19 +1437,31 @@ static int launch_join_responses(kb_sim* s, Round& q, uint32_t resp_nodes) {
   const bool wave_on = full_on || head_on;
   { const int rc = dbg_resp_clear(s); if (rc) return rc; }
   if (full_on) {                                   // timed by events on its own dispatch packet
-    klaunch(s, KI_RESP_WAVE, k_resp_wave<false>, dim3(std::min<uint32_t>((resp_nodes + 3) / 4, 4096)), dim3(256), (uint32_t)wlds, d,
-            q.pb, (const uint32_t*)s->resp_nodes, (const uint32_t*)(s->scan_tot + 4), o0, r, s->slow);
+    klaunch_on(s, st, KI_RESP_WAVE, k_resp_wave<false>, dim3(std::min<uint32_t>((resp_nodes + 3) / 4, wcap)), dim3(256), (uint32_t)wlds, d,
+               q.pb, (const uint32_t*)s->resp_nodes, (const uint32_t*)(s->scan_tot + 4), o0, r, rest, restn, phase, (const uint8_t*)s->a2flag);
   } else if (head_on) {
-    klaunch(s, KI_RESP_WAVE, k_resp_wave<true>, dim3(std::min<uint32_t>((resp_nodes + hwaves - 1) / hwaves, 4096)),
-            dim3(64 * hwaves), (uint32_t)(hwaves * hlds), d, q.pb, (const uint32_t*)s->resp_nodes,
-            (const uint32_t*)(s->scan_tot + 4), o0, r, s->slow);
+    klaunch_on(s, st, KI_RESP_WAVE, k_resp_wave<true>, dim3(std::min<uint32_t>((resp_nodes + hwaves - 1) / hwaves, wcap)),
+               dim3(64 * hwaves), (uint32_t)(hwaves * hlds), d, q.pb, (const uint32_t*)s->resp_nodes,
+               (const uint32_t*)(s->scan_tot + 4), o0, r, rest, restn, phase, (const uint8_t*)s->a2flag);
   }
-  // the workgroup path serves what the wave path left: its list (in the wave lists' slow buffer, free
-  // until the tick) when the wave path ran, else every responder
-  klaunch(s, KI_RESP_NODE, k_resp_node, dim3(wave_on ? std::min<uint32_t>(grid, 2 * s->ncu) : grid), dim3(256), (uint32_t)lds, d, q.pb,
-          (const uint32_t*)(wave_on ? s->slow : s->resp_nodes), (const uint32_t*)(wave_on ? d.ctr + C_RESTN : s->scan_tot + 4),
-          o0, r, scratch, wave_on);
+  // the workgroup path serves what the wave path left: its phase's list when the wave path ran, else every
+  // responder
+  klaunch_on(s, st, KI_RESP_NODE, k_resp_node, dim3(wave_on ? std::min<uint32_t>(grid, 2 * s->ncu) : grid), dim3(256), (uint32_t)lds, d, q.pb,
+             (const uint32_t*)(wave_on ? rest : s->resp_nodes), (const uint32_t*)(wave_on ? restn : s->scan_tot + 4),
+             o0, r, scratch, wave_on, phase, (const uint8_t*)s->a2flag);
   return dbg_resp_report(s, r);
+}
+// The Join responses beside the tick: unsharded, rows whose workgroup path needs no HBM scratch (sized for one
+// launch), no per-wave debug reports, and not switched off (KB_DBG_RESP_SERIAL)
+static bool resp_overlap_on(const kb_sim* s) {
+  return !s->xf && !resp_rows_hbm(s) && !s->debug_waves && !(s->d.dbg & KB_DBG_RESP_SERIAL);
+}
+// A1 (and the list and flags of A2's nodes).  It writes bs.join, bs.nfail, last_bcast, the A2 list and a2flag, and
+// reads alive, n and the suspect slots: nothing the Join responses read or write, so it runs ahead of them
+// when they are split around A2
+static void launch_tick_scan(kb_sim* s, Round& q) {
+  klaunch(s, KI_TICK_SCAN, k_tick_scan, dim3(gnode(s)), dim3(TB), 0, s->d, s->bs, q.r, s->slow, s->a2flag);
+  q.tick_scanned = true;
 }
 
 // Wave 0's outbox regions: the injected records' room, the scan (responses first, then the tick's messages) and
@@ -1465,26 +1497,44 @@ static int round_wave0_regions(kb_sim* s, Round& q) {
     launch_scan(s, a);
   }
   const bool need_tot = s->nj > 0 || q.inj_pay;      // only Joins and injected payloads can outgrow the outbox
-  klaunch(s, KI_SET_CAP, k_set_cap, dim3(gnode(s)), dim3(TB), 0, d, s->nresp, o0.cap, o0.cnt, s->scan_tot, s->d_pin, need_tot ? ++s->pin_seq : 0u);
+  klaunch(s, KI_SET_CAP, k_set_cap, dim3(gnode(s)), dim3(TB), 0, d, s->nresp, o0.cap, o0.cnt, s->scan_tot, s->d_pin, need_tot ? ++s->pin_seq : 0u,
+          s->rest2n);
   if (!need_tot) return KB_OK;
   const uint32_t* tot = s->h_pin;                    // written by k_set_cap through the host mapping
   { const int rc = wait_pin(s, s->pin_seq); if (rc) return rc; }
   const uint32_t pay_tot = tot[1], msg_tot = tot[2], resp_nodes = tot[4];
   if (msg_tot > o0.msg_cap || pay_tot > o0.pay_cap) { const int rc = grow_wave0(s, msg_tot, pay_tot); if (rc) return rc; }
   if (s->n_ext) { const int rc = round_size_exports(s, msg_tot, pay_tot); if (rc) return rc; }
-  return resp_nodes ? launch_join_responses(s, q, resp_nodes) : KB_OK;
+  if (!resp_nodes) return KB_OK;
+  if (!resp_overlap_on(s)) return launch_join_responses(s, q, resp_nodes, 0);
+  // Around A2: A1 first, for the flags; every unflagged responder on the third stream, forked here
+  // (its inputs are final) and joined ahead of k_tick_post; then the flagged responders on st, ahead of A2.  A
+  // responder's records and ids go to offsets fixed by the scan above, so the order of service does not show.
+  // Phase 2 is enqueued first on purpose: its grid then has the CUs to itself for most of its 0.3 ms while phase 1's
+  // workgroups queue behind it, and the fold and A3 run nearly alone afterwards.  Phase 1 first and the fork behind
+  // it was measured and is no faster than the serial order: phase 1 alone takes 0.10 ms, and phase 2 then runs its
+  // whole length beside the fold and A3, 0.76 ms, and ends after them (profiles/r08a_resp_trace_phase1_first.json).
+  launch_tick_scan(s, q);
+  side_fork(s, 4);
+  { const int rc = launch_join_responses(s, q, resp_nodes, 2); if (rc) return rc; }
+  side_done(s, 4);
+  q.resp_side = true;
+  return launch_join_responses(s, q, resp_nodes, 1);
 }
 
 // 3. tick: A1, A2, the fold and the row fingerprints, with the exact A3 order (side work 2) beside the fold; side
-// work 0, 1 and 2 join here.  Then the injected records' emissions and the round's broadcast lists.  No host wait.
+// work 0, 1 and 2 join here, and side work 4 (the Join responses of the responders A2 cannot touch, when they were split
+// around A2: round_wave0_regions, which then ran A1 already).  Then the injected records' emissions and the round's
+// broadcast lists.  No host wait.
 static int round_tick(kb_sim* s, Round& q) {
   Dev& d = s->d;
   const int32_t r = q.r;
   const uint32_t R = s->R, gn = gnode(s);
   OutBuf& o0 = s->ob[0];
   if (q.lat_fail) side_join(s, 1);
-  klaunch(s, KI_TICK_SCAN, k_tick_scan, dim3(gn), dim3(TB), 0, d, s->bs, r, s->slow);                       // A1; list the A2 nodes
-  klaunch(s, KI_TICK_PRE, k_tick_pre, dim3(std::min<uint32_t>((R + 3) / 4, 1024)), dim3(256), 0, d, o0, s->bs, r, s->slow);   // A2 per listed node
+  if (!q.tick_scanned) launch_tick_scan(s, q);                                                               // A1; list the A2 nodes
+  klaunch(s, KI_TICK_PRE, k_tick_pre, dim3(std::min<uint32_t>((R + 3) / 4, 1024)), dim3(256), 0, d, o0, s->bs, r, s->slow,
+          (const uint32_t*)s->nresp);                                                                        // A2 per listed node
   // exact A3 order beside the fold: it reads what A2 left (member bits, stamps, instants, bounds) and writes only
   // the five keys and the bounds, which nothing else reads before k_tick_post; the fold and the row fingerprints
   // write checkpoints and fingerprints only
@@ -1501,6 +1551,7 @@ static int round_tick(kb_sim* s, Round& q) {
   if (d.uniform) klaunch(s, KI_FP_ROWS, k_fp_rows, dim3((FP_LANES * R + TB - 1) / TB), dim3(TB), 0, d);
   side_join(s, 0);
   if (d.tst) side_join(s, 2);
+  if (q.resp_side) side_join(s, 4);                    // k_tick_post appends to the outboxes the responses head
   klaunch(s, KI_TICK_POST, k_tick_post, dim3(gn), dim3(TB), 0, d, s->ro, o0, r);
   if (q.ninj) {                                        // the external peers' wave-0 emissions, after the tick's
     klaunch(s, KI_EVENTS, k_inject, dim3(1), dim3(64), 0, d, o0, (const XRec*)s->d_inj, q.ninj, (const uint32_t*)s->d_inj_ids);

@@ -10,7 +10,7 @@ struct BcastSlots { uint32_t* join; uint32_t* nfail; uint32_t* fail; };
 
 __device__ __attribute__((always_inline)) inline void tick_a2(const Dev& d, const OutBuf& ob, const BcastSlots& bs, int32_t r,
                                                               uint32_t i, uint32_t l, uint32_t* pr, uint32_t* pp,
-                                                              uint32_t* pid) {
+                                                              uint32_t* pid, const uint32_t* nresp) {
   uint32_t n = d.n[i];
   Susp* sl = d.susp + (size_t)i * SLOTS;
   const Susp me = l < SLOTS ? sl[l] : Susp{0, 0, 0, 0};
@@ -123,15 +123,18 @@ __device__ __attribute__((always_inline)) inline void tick_a2(const Dev& d, cons
     }
     bs.nfail[i] = nrem;
     if (nrem) { d.n[i] = n; mark(d, i, segs); slot_add(d, S_RMTIMEOUT, nrem); }
+    if (nrem && nresp[i]) path_hit(d, PATH_A2_RESPONDER);   // coverage: this round's Join responses read this row
     ob.cnt[i] = oseq;
   }
 }
 
 // ---- A1 maybe_broadcast_join (:228-251), thread per node; the nodes with a timed-out suspect slot
-// (A2's only work) are listed for k_tick_pre, a wave per listed node
-__global__ __launch_bounds__(256) void k_tick_scan(Dev d, BcastSlots bs, int32_t r, uint32_t* list) {
+// (A2's only work) are listed for k_tick_pre, a wave per listed node, and flagged (a2flag[i] = 1, else 0): only
+// their rows can change before the window, which is what lets the other Join responders be served beside the tick
+__global__ __launch_bounds__(256) void k_tick_scan(Dev d, BcastSlots bs, int32_t r, uint32_t* list, uint8_t* a2flag) {
   const uint32_t i = d.lo + blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= d.hi) return;
+  a2flag[i] = 0;
   if (!d.alive[i]) { bs.join[i] = 0; bs.nfail[i] = 0; return; }
   const int32_t lb = d.last_bcast[i];
   uint32_t j = 0;
@@ -148,17 +151,19 @@ __global__ __launch_bounds__(256) void k_tick_scan(Dev d, BcastSlots bs, int32_t
   uint32_t base = 0;
   if (lane() == (uint32_t)first) base = atomicAdd(&d.ctr[C_TICK], (uint32_t)__popcll(m));
   list[rdl(base, first) + __popcll(m & ((1ull << lane()) - 1ull))] = i;
+  a2flag[i] = 1;
 }
 
 // ---- A2 handle_suspected_peers (:558-653) for the nodes k_tick_scan listed, one wave per node
 // (persistent grid over the list)
-__global__ __launch_bounds__(256) void k_tick_pre(Dev d, OutBuf ob, BcastSlots bs, int32_t r, const uint32_t* list) {
+__global__ __launch_bounds__(256) void k_tick_pre(Dev d, OutBuf ob, BcastSlots bs, int32_t r, const uint32_t* list,
+                                                  const uint32_t* nresp) {
   __shared__ uint32_t s_pick_rank[4][SLOTS * 3], s_pick_peer[4][SLOTS * 3], s_pick_id[4][SLOTS * 3];
   const uint32_t wv = threadIdx.x >> 6;
   const uint32_t l = lane();
   const uint32_t nlist = d.ctr[C_TICK];
   for (uint32_t it = blockIdx.x * 4 + wv; it < nlist; it += gridDim.x * 4) {
-    tick_a2(d, ob, bs, r, list[it], l, s_pick_rank[wv], s_pick_peer[wv], s_pick_id[wv]);
+    tick_a2(d, ob, bs, r, list[it], l, s_pick_rank[wv], s_pick_peer[wv], s_pick_id[wv], nresp);
   }
 }
 
