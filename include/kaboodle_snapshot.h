@@ -40,8 +40,10 @@
  * Validation happens before any device call; each of these is KB_INVALID_ARGUMENT with a text that says which:
  * a short buffer, bad magic, an unknown format_version, a different abi_version or sizeof(kb_config), a checksum
  * mismatch, a section that runs past len or holds values out of range, a shard count that leaves a shard without
- * rows.  On a machine without a GPU a corrupt snapshot is therefore KB_INVALID_ARGUMENT and a valid one
- * KB_NO_DEVICE.
+ * rows.  Rows the engine never writes are refused too, each by name: a row whose ids are not strictly ascending, an
+ * entry with neither x nor a stamp, a based byte above 1 (a row's `based` flag itself is a choice of representation:
+ * either value is accepted for any row, with the entries that go with it).  On a machine without a GPU a corrupt
+ * snapshot is therefore KB_INVALID_ARGUMENT and a valid one KB_NO_DEVICE.
  *
  * What is stored, what is rebuilt.  Whatever a handle derives from its config alone (the base bitset with its
  * prefix counts and folds, the powers of Z, the caps) is rebuilt by creating the handle from the stored config;
@@ -75,8 +77,8 @@ typedef struct kb_snapshot_info {        /* what the header of a snapshot says, 
   uint32_t reserved[7];
 } kb_snapshot_info;
 
-/* The header of a snapshot, validated as kb_sim_restore validates it (everything but the shard count).  A pure
- * host function. */
+/* The header of a snapshot, validated as kb_sim_restore validates it (layout, checksum and the sections' values:
+ * everything but the shard count).  A pure host function. */
 int kb_snapshot_info_of(const void* buf, size_t len, kb_snapshot_info* out);
 
 /* Write the snapshot into buf.  *bytes is its length; buf NULL or cap 0 is a size query.  A cap smaller than the

@@ -194,6 +194,17 @@ static int sn_check_values(const void* buf, const SnHdr& h, const SnSec* sec) {
   if (sum != h.entries) return bad("the rows' lengths do not add up to the entries");
   const uint32_t* ent = sn_at<uint32_t>(buf, sec, SN_ENTRIES);
   for (uint64_t p = 0; p < h.entries; ++p) if ((ent[p] >> 9) >= C) return bad("an entry's id");
+  // rows the engine never writes, which its list routines assume away: sp_lb searches a row as strictly ascending
+  // ids, sp_put keeps no entry without x or a stamp, and `based` is read as a flag
+  const uint8_t* based = sn_at<uint8_t>(buf, sec, SN_BASED);
+  uint64_t p = 0;
+  for (uint32_t i = 0; i < C; ++i) {
+    if (based[i] > 1) return bad("a based flag above 1");
+    for (uint32_t q = 0; q < ne[i]; ++q, ++p) {
+      if (q && (ent[p] >> 9) <= (ent[p - 1] >> 9)) return bad("a row's ids are not strictly ascending");
+      if (!(ent[p] & 0x1FFu)) return bad("an entry with neither x nor a stamp");
+    }
+  }
   const uint32_t* paq_n = sn_at<uint32_t>(buf, sec, SN_PAQ_N);
   const uint32_t* paq = sn_at<uint32_t>(buf, sec, SN_PAQ);
   const uint32_t* a3 = sn_at<uint32_t>(buf, sec, SN_A3CUR);
@@ -225,6 +236,7 @@ extern "C" int kb_snapshot_info_of(const void* buf, size_t len, kb_snapshot_info
   SnHdr h;
   SnSec sec[SN_NSEC];
   { const int rc = sn_parse(buf, len, &h, sec); if (rc) return rc; }
+  { const int rc = sn_check_values(buf, h, sec); if (rc) return rc; }   // as kb_sim_restore: the header's promise
   memset(out, 0, sizeof *out);
   out->format_version = h.format_version; out->abi_version = h.abi_version; out->cfg = h.cfg;
   out->round = h.round; out->alive = h.alive; out->entries = h.entries; out->bytes = h.bytes; out->payload_crc32 = h.payload_crc32;
