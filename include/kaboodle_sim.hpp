@@ -18,6 +18,7 @@
 #include "kaboodle_age.h"
 #include "kaboodle_delta.h"
 #include "kaboodle_islands.h"
+#include "kaboodle_gaps.h"
 
 namespace kb {
 
@@ -167,6 +168,32 @@ class Mesh {
     if (arrays) { r.label.resize(capacity_); r.size.resize(capacity_); }
     check(kb_sim_islands(h_, &r.summary, arrays ? r.label.data() : nullptr, arrays ? r.size.data() : nullptr, r.label.size()),
           "kb_sim_islands");
+    return r;
+  }
+
+  // the gap list (kaboodle_gaps.h; HIP library only, dense handles): the cells the view census counts as missing and
+  // stale, as (row, id) pairs in ascending order.  A list of more than max_pairs pairs stays empty and its *_listed
+  // is 0; the totals are always there.  max_pairs = 0 asks for the totals alone.
+  struct Gaps { kb_gaps summary; std::vector<uint32_t> missing_pairs, stale_pairs; };
+  Gaps gaps(size_t max_pairs = 65536) const {
+    Gaps r;
+    r.missing_pairs.resize(2 * max_pairs); r.stale_pairs.resize(2 * max_pairs);
+    check(kb_sim_gaps(h_, &r.summary, max_pairs ? r.missing_pairs.data() : nullptr, max_pairs,
+                      max_pairs ? r.stale_pairs.data() : nullptr, max_pairs), "kb_sim_gaps");
+    r.missing_pairs.resize(2 * r.summary.missing_listed); r.stale_pairs.resize(2 * r.summary.stale_listed);
+    return r;
+  }
+  // the holders query: for each of 1 .. KB_HOLDERS_MAX ids the running rows whose view holds it; query q's rows are
+  // rows[offsets[q]] .. rows[offsets[q + 1] - 1], ascending
+  struct Holders { std::vector<uint64_t> offsets; std::vector<uint32_t> rows; };
+  Holders holders(const std::vector<uint32_t>& ids) const {
+    Holders r;
+    r.offsets.resize(ids.size() + 1);
+    uint64_t n = 0;
+    check(kb_sim_holders(h_, ids.data(), ids.size(), r.offsets.data(), nullptr, 0, &n), "kb_sim_holders");
+    if (!n) return r;
+    r.rows.resize(n);                               // the state does not change between the two calls
+    check(kb_sim_holders(h_, ids.data(), ids.size(), r.offsets.data(), r.rows.data(), r.rows.size(), &n), "kb_sim_holders");
     return r;
   }
 

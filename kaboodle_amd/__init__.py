@@ -171,6 +171,21 @@ class Mesh(Sim):
         KbError."""
         return super().islands(arrays)
 
+    def gaps(self, max_pairs: int = 65536) -> dict:
+        """Which rows lack or still hold which ids (include/kaboodle_gaps.h): the cells the view census
+        counts as `missing` and `stale`, listed on the GPU as (row, id) pairs in ascending order.  Returns the fields
+        of kb_gaps and `missing_pairs` / `stale_pairs` as (n, 2) uint32 arrays; a list of more than max_pairs pairs
+        is None and only counted.  Dense rows, unsharded or in-process shards; sparse rows and rank shards raise
+        KbError."""
+        return super().gaps(max_pairs)
+
+    def holders(self, ids, max_rows: int | None = None):
+        """Who holds these ids (include/kaboodle_gaps.h): for each of up to 1,024 ids the running rows
+        whose view contains it, cut out of the member table as columns on the GPU.  Returns (offsets, rows); query q's
+        holders are rows[offsets[q]:offsets[q + 1]], ascending.  Dense rows, unsharded or in-process shards; sparse
+        rows and rank shards raise KbError."""
+        return super().holders(ids, max_rows)
+
 
 def latency_census_of(lat, member, running, arrays: bool = True, device: int = 0):
     """The latency census's GPU kernel over host arrays (kb_latency_census_of, a test surface): `lat` peer-major

@@ -235,6 +235,19 @@ class KbIslands(C.Structure):
 _ISLANDS_OUT = [C.POINTER(KbIslands), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t]
 
 
+KB_HOLDERS_MAX = 1024            # ids one kb_sim_holders call answers
+
+
+class KbGaps(C.Structure):
+    """kb_gaps (include/kaboodle_gaps.h)."""
+    _fields_ = [("round", C.c_int32), ("observers", C.c_uint32), ("missing", C.c_uint64), ("stale", C.c_uint64),
+                ("missing_listed", C.c_uint64), ("stale_listed", C.c_uint64), ("rows_missing", C.c_uint32),
+                ("rows_stale", C.c_uint32), ("reserved", C.c_uint64 * 4)]
+
+    def as_dict(self) -> dict:
+        return _summary(self)
+
+
 KB_SNAPSHOT_VERSION = 1
 
 
@@ -446,6 +459,14 @@ _OPTIONAL = {
     "sim_islands": (C.c_int, [C.c_void_p, *_ISLANDS_OUT]),
     "sim_islands_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "islands_of": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_size_t, *_ISLANDS_OUT]),
+    # the gap list and the holders query (include/kaboodle_gaps.h; HIP library only, the oracle answers through
+    # gaps.gaps_of_sim / gaps.holders_of_sim)
+    "sim_gaps": (C.c_int, [C.c_void_p, C.POINTER(KbGaps), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32),
+                           C.c_size_t]),
+    "sim_gaps_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "sim_holders": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                              C.c_size_t, C.POINTER(C.c_uint64)]),
+    "sim_holders_device_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     # snapshot and restore (include/kaboodle_snapshot.h; HIP library only)
     "snapshot_info_of": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(KbSnapshotInfo)]),
     "sim_snapshot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
@@ -954,6 +975,56 @@ class Sim:
         """Device time of the last islands() in ms (kb_sim_islands_device_ms; HIP library only); 0.0 before the
         first answer."""
         return self._device_ms("islands")
+
+    def gaps(self, max_pairs: int = 65536) -> dict:
+        """The gap list (include/kaboodle_gaps.h): the fields of kb_gaps and `missing_pairs` / `stale_pairs`, the
+        cells the view census counts as missing and stale as (n, 2) uint32 arrays of (row, id), ascending; None for a
+        list of more than max_pairs pairs (the totals are still there).  max_pairs=0: the totals alone.  Computed on
+        the device by kb_sim_gaps (dense handles, unsharded or in-process shards); a library without it (the CPU
+        oracle) answers the same call through gaps.gaps_of_sim, so both are compared through identical calls."""
+        if "sim_gaps" not in self.lib.fn:
+            from .gaps import gaps_of_sim
+            return gaps_of_sim(self, max_pairs)
+        import numpy as np
+        out = KbGaps()
+        bufs = [np.empty((max_pairs, 2), dtype=np.uint32) if max_pairs else None for _ in range(2)]
+        args = [a for b in bufs for a in (b.ctypes.data_as(C.POINTER(C.c_uint32)) if max_pairs else None, max_pairs)]
+        self.lib.call("sim_gaps", self.h, C.byref(out), *args)
+        d = out.as_dict()
+        for name, b in zip(("missing", "stale"), bufs):
+            listed = max_pairs and d[name] <= max_pairs
+            d[name + "_pairs"] = b[: d[name]].copy() if listed else None
+        return d
+
+    def gaps_device_ms(self) -> float:
+        """Device time of the last gaps() in ms (kb_sim_gaps_device_ms; HIP library only); 0.0 before the first
+        answer."""
+        return self._device_ms("gaps")
+
+    def holders(self, ids, max_rows: int | None = None):
+        """The holders query (include/kaboodle_gaps.h): for each of 1 .. KB_HOLDERS_MAX ids the observers whose view
+        holds it.  Returns (offsets, rows): offsets uint64 [len(ids) + 1], rows uint32 with query q's observers
+        ascending at rows[offsets[q]:offsets[q + 1]]; rows is None when there are more than max_rows of them (default:
+        no limit).  Computed on the device by kb_sim_holders (dense handles, unsharded or in-process shards); a
+        library without it (the CPU oracle) answers the same call through gaps.holders_of_sim."""
+        if "sim_holders" not in self.lib.fn:
+            from .gaps import holders_of_sim
+            return holders_of_sim(self, ids, max_rows)
+        import numpy as np
+        q = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        cap = len(q) * self.capacity if max_rows is None else int(max_rows)
+        off = np.zeros(len(q) + 1, dtype=np.uint64)
+        rows = np.empty(cap, dtype=np.uint32) if cap else None        # untouched pages cost nothing
+        n = C.c_uint64(0)
+        self.lib.call("sim_holders", self.h, q.ctypes.data_as(C.POINTER(C.c_uint32)), len(q),
+                      off.ctypes.data_as(C.POINTER(C.c_uint64)),
+                      rows.ctypes.data_as(C.POINTER(C.c_uint32)) if cap else None, cap, C.byref(n))
+        return off, (rows[: n.value].copy() if cap and n.value <= cap else None)
+
+    def holders_device_ms(self) -> float:
+        """Device time of the last holders() in ms (kb_sim_holders_device_ms; HIP library only); 0.0 before the first
+        answer."""
+        return self._device_ms("holders")
 
     def snapshot(self) -> bytes:
         """The mesh's state after the last completed round as one byte string (kb_sim_snapshot,

@@ -17,8 +17,8 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-result", "-Wno-un
 
 def deps() -> list[str]:
     """Every input of the library build (the translation unit and what it includes from this repository)."""
-    return [SRC] + [os.path.join(HERE, "csrc", f) for f in ("kb_device.h", "kb_common.h", "kb_round.h", "kb_tick.h", "kb_waves.h", "kb_xfer.h", "kb_wire.h", "kb_sparse.h", "kb_sparse_host.h", "kb_roundframe.h", "kb_rounddbg.h", "kb_ctl.h", "kb_censusframe.h", "kb_bitpass.h", "kb_scratch.h", "kb_census.h", "kb_recip.h", "kb_classes.h", "kb_latcensus.h", "kb_agecensus.h", "kb_delta.h", "kb_islands.h", "kb_islands_sum.h", "kb_snapshot.h")] + [
-        os.path.join(os.path.dirname(HERE), "include", f) for f in ("kaboodle_sim.h", "kaboodle_census.h", "kaboodle_reciprocity.h", "kaboodle_classes.h", "kaboodle_latency.h", "kaboodle_age.h", "kaboodle_delta.h", "kaboodle_islands.h", "kaboodle_snapshot.h")]
+    return [SRC] + [os.path.join(HERE, "csrc", f) for f in ("kb_device.h", "kb_common.h", "kb_round.h", "kb_tick.h", "kb_waves.h", "kb_xfer.h", "kb_wire.h", "kb_sparse.h", "kb_sparse_host.h", "kb_roundframe.h", "kb_rounddbg.h", "kb_ctl.h", "kb_censusframe.h", "kb_bitpass.h", "kb_scratch.h", "kb_census.h", "kb_recip.h", "kb_classes.h", "kb_latcensus.h", "kb_agecensus.h", "kb_delta.h", "kb_islands.h", "kb_islands_sum.h", "kb_gaps.h", "kb_snapshot.h")] + [
+        os.path.join(os.path.dirname(HERE), "include", f) for f in ("kaboodle_sim.h", "kaboodle_census.h", "kaboodle_reciprocity.h", "kaboodle_classes.h", "kaboodle_latency.h", "kaboodle_age.h", "kaboodle_delta.h", "kaboodle_islands.h", "kaboodle_gaps.h", "kaboodle_snapshot.h")]
 
 
 def needs_build() -> bool:

@@ -335,7 +335,7 @@ __global__ __launch_bounds__(256) void k_lat_column(Dev d, uint32_t node, uint16
 }
 
 namespace kb { struct SpSim; }
-enum CensusMs { CM_VIEW, CM_RECIP, CM_CLASSES, CM_LAT, CM_AGE, CM_DELTA, CM_ISLANDS, CM_N };   // kb_sim::census_ms (kb_censusframe.h)
+enum CensusMs { CM_VIEW, CM_RECIP, CM_CLASSES, CM_LAT, CM_AGE, CM_DELTA, CM_ISLANDS, CM_GAPS, CM_HOLDERS, CM_N };   // kb_sim::census_ms (kb_censusframe.h)
 
 struct kb_sim {
   kb_config cfg;
@@ -459,6 +459,10 @@ struct kb_sim {
   int32_t dl_round = 0;                // the round of the mark
   uint32_t* dl_buf = nullptr;          // the scratch, allocated by the first delta census
   uint32_t* is_buf = nullptr;          // the island census's scratch (kb_islands.h), allocated by its first call
+  // the gap list and the holders query (kb_gaps.h), on the handle whose stream runs them (a group's first shard)
+  uint32_t* gp_buf = nullptr;          // the gap list's scratch, allocated by its first call
+  uint32_t* gp_list = nullptr; size_t gp_list_cap = 0;   // the listed elements of either call, grown on demand
+  char* hd_buf = nullptr; size_t hd_cap = 0;   // the holders query's scratch, bytes; grown with the number of ids asked
 };
 
 // allocation of this handle's device memory; row tables hold the local rows only and their pointer
@@ -2292,6 +2296,9 @@ extern "C" int kb_sim_debug_fold(kb_sim* s, const kb_fold_probe* p) {
 
 // ---- the island census (include/kaboodle_islands.h) ---------------------------------------------------------
 #include "kb_islands.h"
+
+// ---- the gap list and the holders query (include/kaboodle_gaps.h) -------------------------------------------
+#include "kb_gaps.h"
 
 // ---- snapshot and restore (include/kaboodle_snapshot.h) ----------------------------------------------------
 #include "kb_snapshot.h"

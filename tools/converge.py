@@ -19,7 +19,8 @@ records the fingerprint-class census (include/kaboodle_classes.h, DESIGN.md §14
 classes as (fp, size, rep).  With --track-latency the mesh keeps PeerInfo.latency and the record carries the latency
 census's summary too (include/kaboodle_latency.h).  The island census's summary
 (include/kaboodle_islands.h) goes with them: whether the camps the classes show can still merge (one
-island) or are sealed off from each other (several).
+island) or are sealed off from each other (several).  Last come the cells themselves (include/kaboodle_gaps.h,
+DESIGN.md §21): the gap lists, each when it is at most 65,536 pairs, and the rows that still hold the top ghost.
 """
 from __future__ import annotations
 
@@ -126,6 +127,17 @@ def main() -> int:
             # and whether those camps can still reach each other: one island can converge, several cannot
             recip["islands"] = {"summary": m.islands(arrays=False).summary, "device_ms": round(m.islands_device_ms(), 4)}
             print(f"[converge {a.mode}] islands: {json.dumps(recip['islands'])}", flush=True)
+            # and the cells themselves (include/kaboodle_gaps.h): which row lacks which running id and
+            # still holds which dead one, each list when it is at most 65,536 pairs, and who holds the top ghost
+            gp = m.gaps(max_pairs=65536)
+            pairs = {k: None if gp[k] is None else gp[k].tolist() for k in ("missing_pairs", "stale_pairs")}
+            recip["gaps"] = {"summary": {k: v for k, v in gp.items() if k not in pairs}, **pairs,
+                             "device_ms": round(m.gaps_device_ms(), 4)}
+            ghost = recip["census"]["top_ghost"]
+            if ghost != 0xFFFFFFFF:                                    # KB_CENSUS_NONE: no dead id is held
+                recip["gaps"]["top_ghost_holders"] = {"id": ghost, "rows": m.holders([ghost])[1].tolist(),
+                                                      "device_ms": round(m.holders_device_ms(), 4)}
+            print(f"[converge {a.mode}] gaps: {json.dumps(recip['gaps']['summary'])}", flush=True)
             if cfg.track_latency:
                 recip["latency_census"] = {"summary": m.latency_census(arrays=False).summary,
                                            "device_ms": round(m.latency_census_device_ms(), 4)}
